@@ -1,7 +1,15 @@
 """Benchmark: env-steps/s of the batched MergingEnv step on MI355X (BASELINE.json config 3/4).
 
-    python bench.py [--gpus N --steps K --warmup W --envs E]
+    python bench.py [--gpus N --steps K --warmup W --envs E] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU)
+
+A plain run sets up, burns in, warms up, times the K steps and prints the result line (value,
+ms_per_step, the step kernel's roofline from the events around those K launches). --full adds every
+other leg after the timed steps: the per-dispatch event sample, the episode statistics and their
+collective, the fused rollout, replay memory, config-5 and h-DQN legs, the 2^22-env leg, the drop-in
+single env and the CPU baselines. --dump-outputs DIR writes what the last timed step returned
+(DIR/<name>.npy, float32 / float64, a fixed sample of 2^18 env rows when there are more): the inputs
+are the same in every run with the same arguments, so two builds compare output for output.
 
 With --gpus N > 1 and no launcher (no WORLD_SIZE in the environment) bench.py starts the N one-GPU
 ranks itself as child processes, before anything in the parent touches HIP, and exits with the
@@ -26,7 +34,7 @@ or a HIP-graph replay with --graph 1.
 
 Rank 0 prints ONE JSON line: value = env-steps/s over all ranks (max-over-ranks time),
 roofline = algorithmic bytes per launch / mean kernel time (HIP events on the launch stream)
-against the 8 TB/s HBM3E peak, size_2p22 = the same kernel at 2^22 envs (past the 256 MiB
+against the 8 TB/s HBM3E peak; with --full also size_2p22 = the same kernel at 2^22 envs (past the 256 MiB
 Infinity Cache, N = 1 only), cpu_baseline = the CPU restatements on the host cores (rank 0, at every
 world size, after the GPU legs; the other ranks wait at the closing barrier).
 """
@@ -66,6 +74,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs", type=int, default=1 << 20, help="envs per GPU")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: per-dispatch event sample, episode "
+                         "statistics, fused rollout, replay memory, config-5 and h-DQN policies, 2^22 envs, "
+                         "drop-in single env, CPU baselines (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, rew, done, info, the actions drawn) and "
+                         "the env state after it as DIR/<name>.npy, for a fixed seeded sample of env rows")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL, one GPU per rank) or gloo (multi-rank rehearsal, ranks may share a GPU)")
     ap.add_argument("--burn-in", type=int, default=0,
@@ -73,7 +88,7 @@ def parse():
                          "to run, but the window after them starts in the rollout kernel's regime)")
     ap.add_argument("--stagger", type=int, default=256,
                     help="before the burn-in, S one-step launches each followed by a reset of the envs with "
-                         "index % S == j: first-episode phases spread over S steps instead of all envs "
+                         "index mod S == j: first-episode phases spread over S steps instead of all envs "
                          "starting together (tools/size2_probe.py: the finishing rate, and with it the "
                          "per-launch time past the Infinity Cache, otherwise oscillates for thousands of steps)")
     ap.add_argument("--burn-in-launches", type=int, default=1072,
@@ -236,6 +251,41 @@ def capture_steps(step, first: int, count: int, torch):
     return g
 
 
+DUMP_ROWS = 1 << 18  # env rows of --dump-outputs: 160 B per row in all arrays together, 42 MB
+
+
+def snapshot_outputs(env, result, torch):
+    """Host copies of what the last step_random call returned (obs, rew, done, info) with the actions
+    it drew and the env state it left, for the env rows --dump-outputs keeps: all of them up to
+    DUMP_ROWS, else a fixed seeded sample (sorted, the same for every run of the same --envs).
+    float32 / float64 arrays by name; final_observation is meaningful only where done, so the
+    other rows (left over from earlier steps) are written as 0."""
+    import numpy as np
+
+    E = env.num_envs
+    rows = np.arange(E) if E <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(E, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(env.device)
+    obs, rew, done, info = result
+    take = lambda t, dt: t.index_select(0, idx).to(dt).cpu().numpy()  # noqa: E731
+    out = {"env_index": rows.astype(np.float64), "obs": take(obs, torch.float32), "rew": take(rew, torch.float32),
+           "done": take(done, torch.float32), "collision": take(info["collision"], torch.float32),
+           "a1": take(env.a1_buf, torch.float32), "a2": take(env.a2_buf, torch.float32)}
+    if "final_observation" in info:
+        out["final_observation"] = np.where(out["done"][:, None] != 0, take(info["final_observation"], torch.float32),
+                                            np.float32(0.0))
+    for name in ("p1", "v1", "p2", "v2", "ret1", "ret2"):
+        out["state_" + name] = take(getattr(env, name), torch.float64)
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def size2_env(args, torch):
     from merging_gym import MergeVecEnv
 
@@ -297,6 +347,41 @@ def size2_leg(args, torch, env=None):
             "value": E / (kernel_ms * 1e-3), "unit": "env-steps/s", "achieved": achieved, "peak": HBM_PEAK_GBPS,
             "unit_bw": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "frac_8d": frac_8d, "traffic": load_pmc(E),
             "episodes_completed": completed, "episodes_counted_since": "the clear before the burn-in launches"}
+
+
+def episodes_leg(env, args, world, torch, completed_since_clear, launches_since_clear):
+    """The step leg's episode statistics, reduced on the device and gathered over the ranks (see the
+    comment at its call in main()), with the times of the reduction and of the collective."""
+    from merging_gym.distributed import (NUM_COUNTS, NUM_RETURNS, PARTIAL_BYTES, gather_episode_stats,
+                                         gather_episode_summary, summarize)
+
+    timings = {}
+    torch.cuda.synchronize()
+    if world > 1 and args.gather == "per-env":
+        g0 = time.perf_counter()
+        rows = gather_episode_stats(env.returns, env.counts)
+        torch.cuda.synchronize()
+        timings["allgather_ms"] = (time.perf_counter() - g0) * 1e3
+        g0 = time.perf_counter()
+        episodes = summarize(*rows)
+        timings["reduce_ms"] = (time.perf_counter() - g0) * 1e3
+        payload = env.num_envs * (NUM_RETURNS + NUM_COUNTS // 2) * 8
+    else:
+        episodes = gather_episode_summary(env.returns, env.counts, timings=timings)
+        payload = PARTIAL_BYTES if world > 1 else 0
+    episodes["mean_q_eval"] = None  # random actions: no Q-net evaluates them (main.py:221 logs a DQN's value)
+    episodes.update(allgather_ms=timings.get("allgather_ms"), reduce_ms=timings.get("reduce_ms"),
+                    reduce_wall_ms=timings.get("reduce_wall_ms"),
+                    reduce_how=("mg_stats_reduce, fixed order (64 B of records per env): reduce_ms = HIP events "
+                                "around its two launches, reduce_wall_ms = the Python call on the host clock"),
+                    allgather_bytes_per_rank=payload,
+                    completed_rank0=completed_since_clear,
+                    counted_since=(f"the statistics clear before the burn-in launches: {launches_since_clear} launches "
+                                   "(burn-in, warm-up, timed window)"),
+                    logged_as=("mean_return_ego / win_rate_hdqn: hdqn.py:312, :342 (terminal observation); "
+                               "mean_ep_reward_main / win_rate_main: main.py:209-211, :225 (winner-filtered "
+                               "reward, pre-terminal observation); ego_first_rate: winner == 1"))
+    return episodes
 
 
 def rollout_leg(env, args, world, dist, torch):
@@ -936,13 +1021,15 @@ def main():
     gc.enable()
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
     k0 += args.steps
-    completed_since_clear = int(env.counts[:, 0].sum())
     del graph
+    if args.dump_outputs and rank == 0:  # before any other leg steps the envs further
+        write_outputs(args.dump_outputs, snapshot_outputs(env, env._outputs(), torch))
+    completed_since_clear = int(env.counts[:, 0].sum()) if args.full else None
 
     # untimed: per-dispatch durations (events written by the dispatch packets themselves,
     # hipExtLaunchKernel via mg_time_next_launch) for a sample of launches, for reference
     dispatch_ms = None
-    if not args.no_events:
+    if args.full and not args.no_events:
         from merging_gym.profiling import KernelTimer
 
         nsamp = max(1, min(64, args.steps // max(1, args.event_every)))
@@ -965,35 +1052,9 @@ def main():
     # reference's scripts log: each rank reduces its shard on the device to 80 bytes of totals,
     # which one RCCL all-gather (xGMI) brings to every rank, outside the timed loop. The device
     # reduction and the collective are timed apart; at world size 1 there is no collective.
-    from merging_gym.distributed import (NUM_COUNTS, NUM_RETURNS, PARTIAL_BYTES, gather_episode_stats,
-                                         gather_episode_summary, summarize)
-
-    timings = {}
-    torch.cuda.synchronize()
-    if world > 1 and args.gather == "per-env":
-        g0 = time.perf_counter()
-        rows = gather_episode_stats(env.returns, env.counts)
-        torch.cuda.synchronize()
-        timings["allgather_ms"] = (time.perf_counter() - g0) * 1e3
-        g0 = time.perf_counter()
-        episodes = summarize(*rows)
-        timings["reduce_ms"] = (time.perf_counter() - g0) * 1e3
-        payload = E * (NUM_RETURNS + NUM_COUNTS // 2) * 8
-    else:
-        episodes = gather_episode_summary(env.returns, env.counts, timings=timings)
-        payload = PARTIAL_BYTES if world > 1 else 0
-    episodes["mean_q_eval"] = None  # random actions: no Q-net evaluates them (main.py:221 logs a DQN's value)
-    episodes.update(allgather_ms=timings.get("allgather_ms"), reduce_ms=timings.get("reduce_ms"),
-                    reduce_wall_ms=timings.get("reduce_wall_ms"),
-                    reduce_how=("mg_stats_reduce, fixed order (64 B of records per env): reduce_ms = HIP events "
-                                "around its two launches, reduce_wall_ms = the Python call on the host clock"),
-                    allgather_bytes_per_rank=payload,
-                    completed_rank0=completed_since_clear,
-                    counted_since=(f"the statistics clear before the burn-in launches: {launches_since_clear} launches "
-                                   "(burn-in, warm-up, timed window)"),
-                    logged_as=("mean_return_ego / win_rate_hdqn: hdqn.py:312, :342 (terminal observation); "
-                               "mean_ep_reward_main / win_rate_main: main.py:209-211, :225 (winner-filtered "
-                               "reward, pre-terminal observation); ego_first_rate: winner == 1"))
+    episodes = None
+    if args.full:
+        episodes = episodes_leg(env, args, world, torch, completed_since_clear, launches_since_clear)
 
     # the step kernel past the Infinity Cache, after every other leg by default. Rounds 2-3 saw it
     # 2.2-2.6x slower there in one 100-launch window; per-window timing (r03e) showed a one-time
@@ -1001,25 +1062,26 @@ def main():
     # equal (tools/placement_probe.py): with the collector off and one rehearsal window, first /
     # last / last with the env allocated before the legs measure 104.9 / 105.0 / 105.2 us (r03h)
     size2 = None
-    do_size2 = world == 1 and args.size2_envs > 0 and args.size2_envs != E
+    do_size2 = args.full and world == 1 and args.size2_envs > 0 and args.size2_envs != E
     env2 = size2_env(args, torch) if do_size2 and args.size2_prealloc else None
     if do_size2 and args.size2_when == "first":
         size2 = size2_leg(args, torch, env2)
         env2 = None
 
+    legs = args.full and args.rollout_steps > 0
     rollout = None
-    if args.rollout_steps > 0:
+    if legs:
         rollout = rollout_leg(env, args, world, dist, torch)
     replay = None
-    if args.replay_stores > 0 and args.rollout_steps > 0:
+    if legs and args.replay_stores > 0:
         replay = replay_leg(env, args, torch)
 
     qnet = None
-    if args.qnet_launches > 0 and args.rollout_steps > 0:
+    if legs and args.qnet_launches > 0:
         qnet = [qnet_leg(env, args, world, dist, torch, opp) for opp in ("none", "self", "other")]
 
     hdqn = None
-    if args.qnet_launches > 0 and args.rollout_steps > 0:
+    if legs and args.qnet_launches > 0:
         hdqn = hdqn_leg(env, args, world, dist, torch)
 
     if do_size2 and args.size2_when == "last":
@@ -1034,7 +1096,7 @@ def main():
     cpu = dropin = None
     if world > 1:
         dist.barrier()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         dropin = dropin_leg(args.seed)
         cpu = cpu_baseline(args.cpu_seconds, E)
         cpu["ran_while"] = ("the other ranks wait at the closing barrier" if world > 1 else "alone")
@@ -1053,6 +1115,7 @@ def main():
                      "gpus_requested": args.gpus},
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1086,8 +1149,9 @@ def main():
                          "host_sync": "spin" if spin_rc == 0 else "default",
                          "wall_over_kernel": (elapsed / args.steps * 1e3) / kernel_ms if kernel_ms else None,
                          "traffic_rule": "2 x FETCH_SIZE + WRITE_SIZE per launch, profiles/pmc_traffic.json"},
-            "episodes": episodes,
         }
+        if episodes is not None:
+            line["episodes"] = episodes
         valu = load_valu()
         if rollout is not None:
             if "rollout_kernel" in valu:  # VALU-issue roofline of the rollout (VALU, not HBM, bound)
@@ -1128,8 +1192,8 @@ def compact_line(line):
     """The bench contract's ONE JSON line, kept under ~6 KB: every leg's value, roofline fraction,
     mean kernel time and traffic; the per-leg details (VALU counters, episode statistics, notes) are
     on the earlier "bench detail:" line."""
-    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-            "vs_baseline", "dtype", "data", "config", "dist", "build", "stagger")
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "full", "ms_per_step", "higher_is_better",
+            "scaling", "vs_baseline", "dtype", "data", "config", "dist", "build", "stagger")
     out = {k: line[k] for k in keep if k in line}
     rf = line["roofline"]
     out["roofline"] = {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel",
@@ -1140,9 +1204,10 @@ def compact_line(line):
         out["cpu_baseline"] = ({"error": cb["error"][-300:]} if "error" in cb else
                                {k: cb.get(k) for k in ("value", "unit", "cores", "kind", "sample", "ran_while")})
     legs = {}
-    ep = line.get("episodes") or {}
-    legs["step_episodes"] = {k: ep.get(k) for k in ("completed", "collision_rate", "win_rate_hdqn", "allgather_ms",
-                                                   "reduce_ms")}
+    ep = line.get("episodes")
+    if ep is not None:  # a --full run
+        legs["step_episodes"] = {k: ep.get(k) for k in ("completed", "collision_rate", "win_rate_hdqn",
+                                                       "allgather_ms", "reduce_ms")}
     if "size_2p22" in line:
         z = line["size_2p22"]
         legs["size_2p22"] = {k: z.get(k) for k in ("envs", "value", "kernel_ms", "frac", "frac_8d", "traffic")}

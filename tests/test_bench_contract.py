@@ -358,6 +358,76 @@ def test_sync_spin_sets_the_flags_on_the_ranks_own_device(monkeypatch, local, co
     assert fake.calls == expect
 
 
+def test_plain_run_is_the_default_and_its_line_has_no_other_legs(monkeypatch):
+    """Without --full the benchmark times its K steps only: the option is off by default, and the
+    compact line of such a record carries the headline keys and no leg of another workload."""
+    import sys
+
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "some/dir"
+    line = _synthetic(1, with_cpu=False)
+    line["full"] = False
+    out = bench.compact_line(line)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "full"):
+        assert k in out, k
+    assert out["legs"] == {} and "cpu_baseline" not in out
+
+
+class _FakeEnv:
+    """The attributes bench.snapshot_outputs reads, as CPU tensors with a recognisable value per row."""
+
+    def __init__(self, torch, n):
+        r = torch.arange(n)
+        self.num_envs, self.device = n, torch.device("cpu")
+        self.obs = (r[:, None] * 10 + torch.arange(10)).to(torch.float32)
+        self.rew = torch.stack([r, -r], 1).to(torch.float32)
+        self.done = (r % 3 == 0)
+        self.coll = (r % 6 == 0)
+        self.a1_buf, self.a2_buf = (r % 5).to(torch.int8), ((r + 1) % 5).to(torch.int8)
+        self.final_obs = torch.full((n, 10), float("nan"))
+        self.final_obs[self.done] = 7.0
+        for i, name in enumerate(("p1", "v1", "p2", "v2", "ret1", "ret2")):
+            setattr(self, name, r.to(torch.float64) + i / 8)
+        self.result = (self.obs, self.rew, self.done, {"collision": self.coll, "final_observation": self.final_obs})
+
+
+def test_dumped_outputs_are_a_fixed_sample_of_rows_in_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: every array is float32 / float64, the rows kept are the same from call to
+    call (all of them for a small batch, a seeded sorted sample above DUMP_ROWS), each row's values
+    are that env's, and the whole dump of the default batch stays below 64 MB."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    env = _FakeEnv(torch, 1000)
+    full = bench.snapshot_outputs(env, env.result, torch)
+    assert np.array_equal(full["env_index"], np.arange(1000)) and full["obs"].shape == (1000, 10)
+    default_rows = bench.DUMP_ROWS
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    a, b = (bench.snapshot_outputs(env, env.result, torch) for _ in range(2))
+    rows = a["env_index"].astype(np.int64)
+    assert len(rows) == 64 and np.all(np.diff(rows) > 0) and rows.max() < 1000
+    assert set(a) == {"env_index", "obs", "rew", "done", "collision", "a1", "a2", "final_observation", "state_p1",
+                      "state_v1", "state_p2", "state_v2", "state_ret1", "state_ret2"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and len(a[k]) == 64, k
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["obs"][:, 3], rows * 10 + 3) and np.array_equal(a["rew"][:, 1], -rows)
+    assert np.array_equal(a["done"], rows % 3 == 0) and np.array_equal(a["a2"], (rows + 1) % 5)
+    assert np.array_equal(a["state_v2"], rows + 3 / 8) and a["state_v2"].dtype == np.float64
+    assert np.array_equal(a["final_observation"], np.where((rows % 3 == 0)[:, None], 7.0, np.zeros((1, 10))))  # no NaN rows
+    bench.write_outputs(str(tmp_path / "d"), a)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in a)
+    assert np.array_equal(np.load(tmp_path / "d" / "obs.npy"), a["obs"])
+    per_row = sum(x[0].nbytes for x in a.values())
+    assert per_row * default_rows <= 64e6
+
+
 def test_replay_traffic_record_is_consistent():
     """profiles/pmc_replay.json (tools/profile_pmc_replay.py, FETCH_SIZE / WRITE_SIZE passes): the
     store's bytes are the sum of its three kernels', the calibration kernels read back the bytes
