@@ -487,8 +487,9 @@ int mg_observe(const mg_params* params, const mg_state* state, const mg_outputs*
  * The same step, reset and observation functions the kernels run, compiled for the host and applied
  * to HOST pointers, synchronously, one env after another: every output and condition is exactly
  * mg_step's / mg_reset's / mg_observe's (done_mask / won_mask words per 64 envs included), and the
- * doubles are the kernel's bit for bit (the host build has no contraction either; sin / cos for
- * |theta| >= 1/16, off every live-episode state, are glibc's there). For one env at the scripts'
+ * doubles are the kernel's bit for bit (the host build has no contraction either), except that sin /
+ * cos for |theta| >= 1/16 are glibc's there and the device library's on the GPU, within 1 ulp of each
+ * other: live episodes do reach such angles once a car has arrived. For one env at the scripts'
  * pace (merging_env.py:138-230 called per step, scripts/human_player.py:112-187) a step costs
  * ~1 us here against a kernel launch plus a stream synchronisation on the GPU; batches belong on
  * the device (mg_step and the rollout kernels). */

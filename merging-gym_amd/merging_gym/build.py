@@ -2,7 +2,8 @@
 
 hipcc --offload-arch=gfx950, -ffp-contract=off (the step's fp64 arithmetic must not be
 fused: positions and arrival tests are compared bit-for-bit with the reference's floats).
-The library carries the sha256 of the source, header and flags it was built from (mg_build_info);
+The library carries the sha256 of the source (merging_hip.hip and the parts it includes), header and
+flags it was built from (mg_build_info);
 build() recompiles when that differs from the tree's, and merging_gym._native refuses (or rebuilds)
 a stale in-tree library at import.
 """
@@ -11,6 +12,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -36,13 +38,37 @@ def hipcc() -> str:
 HEADER = os.path.join(INCLUDE, "merging_hip.h")
 
 
+def source_files(src: str = SRC) -> list[str]:
+    """The translation unit and every part it includes, directly or through another part: the
+    quoted includes that resolve beside the including file (the compiler's own rule), in the order
+    met. The C-ABI header lives under include/ and is not one of them."""
+    files, todo = [], [src]
+    while todo:
+        path = todo.pop(0)
+        if path in files:
+            continue
+        files.append(path)
+        with open(path, "r", errors="replace") as f:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read(), re.M)
+        todo += [q for q in (os.path.join(os.path.dirname(path), n) for n in names) if os.path.isfile(q)]
+    return files
+
+
+# all that source_sha() covers besides the flags, for tools (an installed package has no csrc/)
+SOURCES = (source_files() if os.path.exists(SRC) else []) + [HEADER]
+
+
 def source_sha(src: str = SRC, header: str = HEADER) -> str:
-    """sha256 (first 16 hex digits) of the kernel source, the C-ABI header and the compiler flags:
-    embedded in the library (mg_build_info "src <sha>") so a build can be matched to its tree."""
+    """sha256 (first 16 hex digits) of the kernel source (the translation unit and every part it
+    includes, each under its file name, so text moved between parts is another source), the C-ABI
+    header and the compiler flags: embedded in the library (mg_build_info "src <sha>") so a build
+    can be matched to its tree."""
     h = hashlib.sha256()
-    for path in (src, header):
+    for path in (*source_files(src), header):
+        h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())
+        h.update(b"\0")
     h.update(" ".join(HIPCC_FLAGS).encode())
     return h.hexdigest()[:16]
 

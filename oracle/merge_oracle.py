@@ -444,7 +444,7 @@ def _bf16(a):
 
 
 def _bias_parts(b):
-    """merging_hip.hip qnet_pack_kernel's three-way split b = hi + mid + lo of an fp32 bias into bf16
+    """csrc/mg_qnet.h qnet_pack_kernel's three-way split b = hi + mid + lo of an fp32 bias into bf16
     parts (the padded K slots whose input is 1.0)."""
     b = np.asarray(b, np.float32)
     hi = _bf16(b)
@@ -454,11 +454,11 @@ def _bias_parts(b):
     return hi, mid, lo
 
 
-def _unit1(kb, g, j):  # merging_hip.hip qnet_unit1: hidden-1 unit at k = 8 g + j of layer-2 k-block kb
+def _unit1(kb, g, j):  # csrc/mg_qnet.h qnet_unit1: hidden-1 unit at k = 8 g + j of layer-2 k-block kb
     return 32 * kb + (j & 3) + 8 * (j >> 2) + 16 * (g & 1) + 4 * (g >> 1)
 
 
-def _unit2(kb, g, j):  # merging_hip.hip qnet_unit2: hidden-2 unit at k = 8 g + j of layer-3 k-block kb
+def _unit2(kb, g, j):  # csrc/mg_qnet.h qnet_unit2: hidden-2 unit at k = 8 g + j of layer-3 k-block kb
     return 32 * kb + 16 * (j >> 2) + 4 * g + (j & 3)
 
 

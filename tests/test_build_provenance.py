@@ -26,6 +26,22 @@ def test_touching_the_source_makes_the_library_stale(tmp_path):
     assert not build.is_current(str(lib), build.source_sha(str(src), str(hdr)))
     hdr.write_text("#define X 2\n")
     assert build.source_sha(str(src), str(hdr)) != sha
+    # a part the translation unit includes (through another part) is source too, under its name
+    part, inner = tmp_path / "mg_part.h", tmp_path / "mg_inner.h"
+    src.write_text('#include "mg_part.h"\n__global__ void k() {}\n')
+    part.write_text('#pragma once\n#include "mg_inner.h"\n')
+    inner.write_text("#pragma once\nconstexpr int kA = 3;\n")
+    assert build.source_files(str(src)) == [str(src), str(part), str(inner)]
+    sha = build.source_sha(str(src), str(hdr))
+    lib.write_bytes(b"\x7fELF...; src " + sha.encode() + b"\x00rest")
+    assert build.is_current(str(lib), build.source_sha(str(src), str(hdr)))
+    inner.write_text("#pragma once\nconstexpr int kA = 4;\n")  # one byte of an included part
+    assert not build.is_current(str(lib), build.source_sha(str(src), str(hdr)))
+    inner.write_text("#pragma once\nconstexpr int kA = 3;\n")
+    assert build.is_current(str(lib), build.source_sha(str(src), str(hdr)))
+    part.write_text('#pragma once\n#include "mg_inner.h"\nconstexpr int kA = 3;\n')  # the same text moved
+    inner.write_text("#pragma once\n")
+    assert not build.is_current(str(lib), build.source_sha(str(src), str(hdr)))
 
 
 def test_a_library_without_a_source_sha_is_stale(tmp_path):

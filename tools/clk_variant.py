@@ -1,20 +1,17 @@
 """Phase-clock instrumentation of the h-DQN / config-5 kernels (a diagnostic build, never shipped):
 each wave of blocks 0..63 stamps s_memtime at the start of every phase and just before the phase's
 closing barrier into a device array that mg_debug_clocks copies out. Applied as text edits to a
-source file (the shipped one or an older one):
+temporary copy of a translation unit and the parts it includes (the shipped merging_hip.hip or an
+older single-file one); each edit must match across them exactly as often as it says:
 
     python tools/clk_variant.py SRC OUT.so [0|1|base|q5|q5base]
 
 (0 / 1 / base: the h-DQN kernel's phases, with the round-5 or round-4 forward marks; q5 / q5base:
 the config-5 kernel's, working tree or round-4 source.)
 """
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "merging-gym_amd"))
-from merging_gym import build  # noqa: E402
+from ab_source import compile_edited
 
 HDR = '''
 __device__ unsigned g_mg_clk[64 * 8 * 64 * 16];
@@ -236,21 +233,11 @@ EDITS = [
 
 
 def main(src, out, marks="0"):
-    s = open(src).read()
-    s = s.replace('#include "merging_hip.h"\n', '#include "merging_hip.h"\n' + HDR, 1)
     sets = {"0": EDITS, "1": EDITS + NEW_EDITS, "base": EDITS + BASE_EDITS,
             "q5": Q5_COMMON + Q5_EDITS, "q5base": Q5_COMMON + Q5_BASE_EDITS, "hnow": EDITS + NOW_EDITS, "hlist": EDITS + LIST_EDITS}
-    for e in sets[marks]:
-        a, b, n = e if len(e) == 3 else (*e, 1)
-        assert s.count(a) == n, a[:80]
-        s = s.replace(a, b)
-    tmp = out + ".hip"
-    open(tmp, "w").write(s)
-    try:
-        subprocess.check_call([build.hipcc(), *build.HIPCC_FLAGS, "-I", build.INCLUDE, "-o", out, tmp])
-    finally:
-        os.unlink(tmp)
-    print(out)
+    edits = [('#include "merging_hip.h"\n', '#include "merging_hip.h"\n' + HDR, 1)]
+    edits += [e if len(e) == 3 else (*e, 1) for e in sets[marks]]
+    compile_edited(src, edits, out)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 // matrix pipe one wave's in-order issue leaves idle (round 6).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include \
 //         -o tools/micro/qfwd32_waves tools/micro/qfwd32_waves.hip && tools/micro/qfwd32_waves
-#include "../../merging-gym_amd/csrc/merging_hip.hip"
+#include "../../merging-gym_amd/csrc/mg_qnet.h"
 
 #include <cstdio>
 #include <vector>

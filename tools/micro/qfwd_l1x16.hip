@@ -8,9 +8,9 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include \
 //         -o tools/micro/qfwd_l1x16 tools/micro/qfwd_l1x16.hip && tools/micro/qfwd_l1x16
 #ifndef MG_SRC
-#include "../../merging-gym_amd/csrc/merging_hip.hip"
+#include "../../merging-gym_amd/csrc/mg_qnet.h"
 #else
-#include MG_SRC  // an edited copy of the source (tools/micro/qfwd_ablate.sh: the forward's parts removed)
+#include MG_SRC  // an edited copy of mg_qnet.h (tools/micro/qfwd_ablate.sh: the forward's parts removed)
 #endif
 
 #include <cstdio>

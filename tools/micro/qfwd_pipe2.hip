@@ -6,7 +6,7 @@
 // Timing and a bit check: the pipelined forwards' Q rows must equal qnet_mlp<D, 2>'s.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include \
 //         -o tools/micro/qfwd_pipe2 tools/micro/qfwd_pipe2.hip && tools/micro/qfwd_pipe2
-#include "../../merging-gym_amd/csrc/merging_hip.hip"
+#include "../../merging-gym_amd/csrc/mg_qnet.h"
 
 #include <cstdio>
 #include <vector>

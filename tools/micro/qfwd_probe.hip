@@ -6,7 +6,7 @@
 // tile per wave in LDS, as in the kernel.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include \
 //         -o tools/micro/qfwd_probe tools/micro/qfwd_probe.hip && tools/micro/qfwd_probe
-#include "../../merging-gym_amd/csrc/merging_hip.hip"
+#include "../../merging-gym_amd/csrc/mg_qnet.h"
 
 #include <cstdio>
 #include <vector>

@@ -2,7 +2,7 @@
 
     python tools/resource_usage.py [extra hipcc flags...]
 
-Compiles merging-gym_amd/csrc/merging_hip.hip for gfx950 into a throw-away object and prints
+Compiles merging-gym_amd/csrc/merging_hip.hip (with merging_gym.build.HIPCC_FLAGS) into a throw-away object and prints
 one line per kernel: VGPRs, AGPRs, SGPRs, spills, scratch, LDS and the occupancy hipcc reports.
 """
 
@@ -15,16 +15,17 @@ import tempfile
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "merging-gym_amd", "csrc", "merging_hip.hip")
+sys.path.insert(0, os.path.join(ROOT, "merging-gym_amd"))
+from merging_gym import build  # noqa: E402
+
 FIELDS = ("VGPRs", "AGPRs", "SGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]",
           "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
 
 
 def main(argv):
     with tempfile.TemporaryDirectory() as td:
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-               "-ffp-contract=off", "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-o",
-               os.path.join(td, "x.so"), SRC, "-Rpass-analysis=kernel-resource-usage", *argv]
+        cmd = [build.hipcc(), *build.HIPCC_FLAGS, "-I", build.INCLUDE, "-o", os.path.join(td, "x.so"), build.SRC,
+               "-Rpass-analysis=kernel-resource-usage", *argv]
         out = subprocess.run(cmd, capture_output=True, text=True)
     if out.returncode:
         sys.stderr.write(out.stderr)

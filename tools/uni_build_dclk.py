@@ -1,11 +1,15 @@
 """Builds tools/variants/lib_dclk.so, a stamped diagnostic copy of the uniform-wave config-5 kernel
 with 64-env items (tools/variants/qnet_uniform_waves_persistent_items.patch) for tools/uni_wave_clk.py.
-Reads the working-tree source, which must hold that kernel (apply the patch first); never shipped."""
+Builds from the source at the commit the patch names in its first line, with the patch applied (not from
+the working tree); never shipped."""
 import os
-import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-s=open(ROOT+'/merging-gym_amd/csrc/merging_hip.hip').read()
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ab_source import compile_text, patched_source  # noqa: E402
+
+s = patched_source(ROOT + "/tools/variants/qnet_uniform_waves_persistent_items.patch")
 HDR = '''
 __device__ unsigned g_mg_clk[64 * 8 * 64 * 16];
 #define MG_STAMP(slot, ev, val) do { if (blockIdx.x < 64 && (threadIdx.x & 63) == 0 && (slot) < 64) \\
@@ -46,7 +50,4 @@ ed=[
 for o,n in ed:
     assert s.count(o)==1, o
     s=s.replace(o,n)
-p=ROOT+'/merging-gym_amd/csrc/.dclk.hip'
-open(p,'w').write(s)
-subprocess.run(["/opt/rocm/bin/hipcc","--offload-arch=gfx950","-O3","-std=c++17","-fPIC","-shared","-ffp-contract=off","-fno-fast-math","-w",'-DMG_SRC_SHA="dclk"',"-I",ROOT+"/include","-o",ROOT+"/tools/variants/lib_dclk.so",p],check=True)
-os.remove(p)
+compile_text(s, ROOT + "/tools/variants/lib_dclk.so", "dclk")

@@ -1,12 +1,16 @@
 """Builds tools/variants/lib_pclk.so, a stamped diagnostic copy of the uniform-wave config-5 kernel
 with the persistent grid (r06ab: tools/variants/qnet_uniform_waves.patch plus the chunk loop of
 qnet_uniform_waves_persistent_items.patch without its LDS item counter) for tools/uni_chunk_clk.py.
-Reads the working-tree source, which must hold that kernel (apply the patch first); never shipped."""
+Builds from the source at the commit the patch names in its first line, with the patch applied (not from
+the working tree); never shipped."""
 import os
-import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-s=open(ROOT+'/merging-gym_amd/csrc/merging_hip.hip').read()
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ab_source import compile_text, patched_source  # noqa: E402
+
+s = patched_source(ROOT + "/tools/variants/qnet_uniform_waves_persistent_items.patch")
 HDR = '''
 __device__ unsigned g_mg_clk[64 * 8 * 64 * 16];
 #define MG_STAMP(slot, ev, val) do { if (blockIdx.x < 64 && (threadIdx.x & 63) == 0 && (slot) < 64) \\
@@ -16,6 +20,15 @@ extern "C" int mg_debug_clocks(void* dst) { return hipMemcpyFromSymbol(dst, HIP_
 anchor="constexpr int kQUniThreads = 512;"
 s=s.replace(anchor, HDR+anchor,1)
 ed=[
+# r06ab's kernel was not kept as a patch of its own: the patch's work-item loop back to whole chunks per block
+("""  for (;;) {
+  int item = 0;
+  if (lane == 0) item = atomicAdd(&next_item, 1);
+  item = __shfl(item, 0);
+  if (item >= items) break;
+  const int64_t wbase = (blockIdx.x + static_cast<int64_t>(item >> 3) * gridDim.x) * kQUniThreads + 64 * (item & 7);""",
+"""  for (int64_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
+  const int64_t wbase = chunk * kQUniThreads + 64 * wave;"""),
 ("""  for (int64_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
   const int64_t wbase = chunk * kQUniThreads + 64 * wave;""",
 """  int ci = 0;
@@ -41,7 +54,4 @@ ed=[
 for o,n in ed:
     assert s.count(o)==1, o
     s=s.replace(o,n)
-p=ROOT+'/merging-gym_amd/csrc/.pclk.hip'
-open(p,'w').write(s)
-subprocess.run(["/opt/rocm/bin/hipcc","--offload-arch=gfx950","-O3","-std=c++17","-fPIC","-shared","-ffp-contract=off","-fno-fast-math","-w",'-DMG_SRC_SHA="pclk"',"-I",ROOT+"/include","-o",ROOT+"/tools/variants/lib_pclk.so",p],check=True)
-os.remove(p)
+compile_text(s, ROOT + "/tools/variants/lib_pclk.so", "pclk")

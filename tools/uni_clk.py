@@ -10,11 +10,9 @@ inside the rollout kernel, and at what clock.
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "merging-gym_amd", "csrc", "merging_hip.hip")
 PATCH = os.path.join(ROOT, "tools", "variants", "qnet_uniform_waves.patch")
 
 HDR = '''
@@ -42,14 +40,10 @@ FWD_ONLY = ("""    qnet_policy_step_n<OPP, 1, CHECKED>(R, e, r, wbase + lane, li
 
 
 def build():
-    src = subprocess.run(["git", "-C", ROOT, "show", "HEAD:merging-gym_amd/csrc/merging_hip.hip"],
-                         capture_output=True, text=True, check=True).stdout
-    tmp = os.path.join(ROOT, "merging-gym_amd", "csrc", ".uniclk_base.hip")
-    open(tmp, "w").write(src)
-    # apply the patch to the copy: patch(1) reads the unified diff
-    subprocess.run(["patch", "-s", tmp, PATCH], check=True)
-    base = open(tmp).read()
-    os.remove(tmp)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from ab_source import compile_text, patched_source
+
+    base = patched_source(PATCH)  # the commit the patch names in its first line, not the working tree
     anchor = "constexpr int kQUniThreads = 512;"
     assert anchor in base
     for name, fwd_only in (("uniclk", False), ("uniclk_fwd", True)):
@@ -60,14 +54,7 @@ def build():
         if fwd_only:
             assert s.count(FWD_ONLY[0]) == 1
             s = s.replace(FWD_ONLY[0], FWD_ONLY[1])
-        path = os.path.join(ROOT, "merging-gym_amd", "csrc", f".{name}.hip")
-        open(path, "w").write(s)
-        out = os.path.join(ROOT, "tools", "variants", f"lib_{name}.so")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                        "-ffp-contract=off", "-fno-fast-math", "-w", "-DMG_SRC_SHA=\"uniclk\"",
-                        "-I", os.path.join(ROOT, "include"), "-o", out, path], check=True)
-        os.remove(path)
-        print(out)
+        compile_text(s, os.path.join(ROOT, "tools", "variants", f"lib_{name}.so"), "uniclk")
 
 
 def run():
