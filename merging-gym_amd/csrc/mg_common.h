@@ -34,6 +34,7 @@ constexpr int kObs = MG_OBS_DIM;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Store of a per-step output (observation, reward, flags, actions): written once, never
 // re-read by the step, so optionally non-temporal. The env state is stored normally: the

@@ -573,7 +573,7 @@ def qnet_reference_mfma(weights, x, swap: bool = False, form: str = "16x16", rul
 
 
 def qnet_policy_draws(words, step, opponent):
-    """The epsilon-greedy draws of mg_rollout_qnet at global step `step` (merging_hip.hip
+    """The epsilon-greedy draws of mg_rollout_qnet at global step `step` (csrc/mg_rollout_qnet.h
     qnet_policy_step_n, ABI 20), restated: words(c) -> [n, 4] uint32 Philox4x32-10 words of counter
     (gi, c) for the envs checked. opponent "none" / "uniform" (two draws per step, one call per two
     steps): words (x, y) of call step div 2 on even steps, (z, w) on odd ones; explore = the first,
@@ -594,7 +594,7 @@ def qnet_policy_draws(words, step, opponent):
 
 def hdqn_fresh_draws(words, step, opponent):
     """The fresh-goal draws (explore, goal word) of mg_rollout_hdqn at global step `step` from stream
-    B (counter gi ^ 2^63; merging_hip.hip fresh_goal_words, ABI 20), restated: words(c) -> [n, 4]
+    B (counter gi ^ 2^63; csrc/mg_rollout_hdqn.h fresh_goal_words, ABI 20), restated: words(c) -> [n, 4]
     uint32 words of counter (gi ^ 2^63, c). Every opponent but "uniform": one call per two steps --
     call step div 2, words (x, y) on even steps, (z, w) on odd ones. "uniform": call `step`, (x, y),
     and z is the opponent's action word. Returns (explore, goal word, uniform-opponent word or None);
@@ -618,7 +618,7 @@ def goal_status64(obs):
 
 
 def stats_reduce_fixed(records):
-    """mg_stats_reduce's totals (include/merging_hip.h, merging_hip.hip stats_reduce_kernel) restated
+    """mg_stats_reduce's totals (include/merging_hip.h, csrc/mg_stats_reduce.h stats_reduce_kernel) restated
     in numpy, operation for operation: records [n, 8] f64 (the 64-byte mg_episode_stats rows) ->
     (four f64 sums of ret[0], ret[1], ret_main, q_eval; six int64 counts). Blocks of 1,024 records; thread t
     of 256 adds records t, t + 256, t + 512, t + 768 of its block onto -0.0 in that order; the 256

@@ -74,7 +74,7 @@ def test_default_params_are_the_reference_constants():
 
 def test_qp_step_constants_reproduce_the_oracle_qp(coracle, golden):
     """The kernel's u0 = (b / qp_nz) * qp_z0, b = vt - v0, or -0.0 where |b| < qp_vsmall
-    (merging_hip.hip mpc_acc) is bit for bit -- sign of zero included -- the first control of the
+    (csrc/mg_env.h mpc_acc) is bit for bit -- sign of zero included -- the first control of the
     oracle's full qpgen2 solve (dpofa, dposl, dpori, the equality step), and of the Python
     restatement, on the golden mpc inputs and on every (action, speed) pair a step can meet,
     including speeds decayed below vsmall under action 0 and speeds equal to the target."""

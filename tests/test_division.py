@@ -1,5 +1,5 @@
 """The kernel divides by R = 30000 and by the QP constant n'P^-1 n = 90.00000000000153 as q = x*inv; r = fma(-q, d, x);
-fma(r, inv, q) (merging_hip.hip div_const). Check on the host that this is the correctly
+fma(r, inv, q) (csrc/mg_env.h div_const). Check on the host that this is the correctly
 rounded quotient x / d, as the reference's Python division is."""
 
 import ctypes

@@ -273,7 +273,7 @@ def test_host_step_equals_kernel_past_the_polynomial_range():
 
 def test_host_collision_test_over_the_whole_plane(coracle):
     """The step's collision test takes integer lateral edges where they equal the fp64 ones (y >= 8,
-    merging_hip.hip vehicles_collide) and the fp64 form elsewhere. Pairs of cars placed over the
+    csrc/mg_env.h vehicles_collide) and the fp64 form elsewhere. Pairs of cars placed over the
     whole reachable plane -- positions far past the end point, where the opponent's mirror arc
     crosses y = 8 and 0, and pairs packed within a few metres of each other around the merge point
     x = 0 -- collide exactly when the C oracle's fp64 boxes do (no autoreset, both cars held still)."""

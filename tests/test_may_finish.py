@@ -1,4 +1,4 @@
-"""may_finish_next (merging_hip.hip): the config-5 kernels evaluate the ego's Q-net for an env whose
+"""may_finish_next (csrc/mg_rollout_qnet.h): the config-5 kernels evaluate the ego's Q-net for an env whose
 next step may end its episode even when the ego explores, because main.py:221 logs
 eval_net(state)[action] of every episode's last step. The predicate must therefore flag EVERY step
 that ends an episode. This restates it in numpy (same fp32 inputs: the observation the kernel keeps
@@ -20,7 +20,7 @@ SMIN, SMAX, G = -0.5, 40.5, (0.2 * 30.000000000000533 / 90.0000000000015) * 1.01
 
 
 def finish_bound(veh_w=4, veh_h=8, R=30000.0, dT=0.2, speeds=(0, 10, 20, 30, 40), start_vel=20.0):
-    """merging_hip.hip finish_bound's collision reach (lat, lon), restated."""
+    """csrc/mg_rollout_qnet.h finish_bound's collision reach (lat, lon), restated."""
     dl = dT * (max(max(speeds), start_vel) + 0.5)
     lat = veh_w + 1.75
     for _ in range(4):
