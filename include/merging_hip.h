@@ -85,7 +85,29 @@ extern "C" {
 #define MG_ST_V1_INT 0x10u /* vel1 is int 0 from max(0, ...) (merging_env.py:149) */
 #define MG_ST_V2_INT 0x20u /* vel2 likewise (merging_env.py:153) */
 
-/* Environment constants, merging_env.py:22-46 and :101. Fill with mg_params_default(). */
+/* Environment constants, merging_env.py:22-46 and :101. Fill with mg_params_default(), then change
+ * what differs. Every field is read by the kernels, and the parity bar of the default values -- flags
+ * exact, fp32 outputs the oracle's fp64 values rounded once, fp64 state bit for bit -- holds across
+ * mg_params (tests/params_cases.py).
+ *
+ * Derived fields: a caller that changes R, H, prediction_t, dT or the time limit recomputes them, as
+ * mg_params_default does for the defaults (tests/params_cases.py fill_native restates it):
+ *   angle0        = atan2(H, R)
+ *   inv_R         = 1 / R, rounded
+ *   end_point     the reference's H - 50 (any value on the road is accepted)
+ *   qp_nz, qp_z0, qp_vsmall   qpgen2's constants for the horizon prediction_t
+ *   qp_inv_nz     = 1 / qp_nz, rounded
+ *   timeout_steps = the first k at which k sequential fp64 additions of dT exceed the time limit
+ *                   (merging_env.py:141-142; 500 s there): dT = 0.1 gives 5000, not 5001.
+ * Accepted ranges, checked on the host by every entry point that takes params (a non-zero return,
+ * mg_last_error() names the field): 1 <= timeout_steps <= 8191 (mg_state.tf's step count saturates
+ * there, so a larger value would never time out); R, dT positive and finite; veh_w, veh_h positive;
+ * inv_R == 1 / R and qp_inv_nz == 1 / qp_nz exactly (the kernels' division needs the rounded
+ * reciprocal of its divisor). Nothing else is checked: an angle0 or a qp constant that does not follow
+ * from the other fields is computed with as given.
+ * One exception to the bar: where |angle0 - pos / R| >= 1/16 (R = 300, say) sin / cos are the device
+ * library's on the GPU and glibc's in the oracle and the host path, one ulp apart, which can move
+ * the collision flag of boxes that exactly touch; there the flags are checked on the host path only. */
 typedef struct mg_params {
   double R;            /* 30000: arc radius                          merging_env.py:22 */
   double H;            /* 1000                                        merging_env.py:23 */

@@ -372,7 +372,7 @@ int mg_replay_sample(const float* rows, const uint64_t* counter, int64_t capacit
 
 int mg_reset(const mg_params* params, const mg_state* state, const uint8_t* mask,
              const mg_outputs* out, int64_t n, void* stream) {
-  if (!params) return fail(hipErrorInvalidValue, "%s", "params is NULL");
+  if (int e = check_params(params)) return e;
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (int e = check_state(state)) return e;
   if (n == 0) return 0;
@@ -441,7 +441,7 @@ int mg_host_step(const mg_params* params, const mg_state* state, const int8_t* a
 
 int mg_host_reset(const mg_params* params, const mg_state* state, const uint8_t* mask,
                   const mg_outputs* out, int64_t n) {
-  if (!params) return fail(hipErrorInvalidValue, "%s", "params is NULL");
+  if (int e = check_params(params)) return e;
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (int e = check_state(state)) return e;
   mg_outputs o{};

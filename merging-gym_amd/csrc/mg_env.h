@@ -136,12 +136,19 @@ MG_HD bool boxes_intersect(const Box& a, const Box& b) {
 }
 
 // is_collided (:198-206) of cars at (lateral y, longitudinal x): boxes_intersect(vehicle_box(y1, x1),
-// vehicle_box(y2, x2)) with the lateral edges as integers where that is exact. For y >= 8 the corner
-// k = trunc(y) - w/2 (or + w/2) lies within [y/2, 2y], so k - y is exact (Sterbenz) and (k - y) + y is
-// k itself: the fp64 lateral edges are the integer ones and their comparison is an integer one. Up to
-// |theta| = 1/16 a lateral coordinate is 150 +- d with d <= 59; a car that drives on after arriving
-// (live episodes do get there) can bring the opponent's mirror arc to y < 8, where the fp64 form stays. Same result as
-// the fp64 test for every input (tests/test_host_step.py drives both on the host).
+// vehicle_box(y2, x2)) with the lateral edges as integers where that is exact. For y >= 8 and the
+// default veh_w / 2 = 2 the corner k = trunc(y) -+ 2 lies within [y/2, 2y], so k - y is exact (Sterbenz)
+// and (k - y) + y is k itself: the fp64 lateral edges are the integer ones and their comparison is an
+// integer one. For wider boxes a corner can leave [y/2, 2y] (y < 2 veh_w) and its fp64 edge can then be
+// k +- an ulp -- but only an edge that decides nothing: y1 >= y2 on the two arcs, so the deciding pair is
+// the ego's left edge against the opponent's right edge, and they are within an ulp of each other only
+// where trunc(y1) - trunc(y2) = veh_w. There y1 >= veh_w, so the ego's k = trunc(y1) - veh_w / 2 is in
+// (0, y1]: k - y1 is a multiple of y1's ulp no larger than y1, hence exact; the opponent's right edge r = trunc(y2) + veh_w - veh_w / 2 >= |r - y2|,
+// so the error of r - y2 (at most half an ulp of r) rounds away again in (r - y2) + y2. Up to
+// |theta| = 1/16 a default lateral coordinate is 150 +- d with d <= 59; a car that drives on after
+// arriving (live episodes do get there) can bring the opponent's mirror arc to y < 8, where the fp64
+// form stays. Same result as the fp64 test for every input (tests/test_host_step.py drives both on the
+// host, wide boxes at small y included).
 MG_HD bool vehicles_collide(const mg_params& P, double y1, double x1, double y2, double x2) {
   if (y1 >= 8.0 && y2 >= 8.0) {
     const int l1 = static_cast<int>(y1) - P.veh_w / 2, l2 = static_cast<int>(y2) - P.veh_w / 2;

@@ -27,8 +27,25 @@ int check_state(const mg_state* s) {
   return 0;
 }
 
-int check_common(const mg_params* p, const mg_state* s, const mg_outputs* o, int64_t n) {
+// The params a launch cannot run with (include/merging_hip.h, mg_params): a few scalar compares per
+// call. The step count of mg_state.tf saturates at MG_TF_STEPS_MASK, so a larger timeout_steps would
+// never time out; div_const needs the rounded reciprocals of its two divisors.
+int check_params(const mg_params* p) {
   if (!p) return fail(hipErrorInvalidValue, "%s", "params is NULL");
+  const char* bad = nullptr;
+  if (p->timeout_steps < 1 || p->timeout_steps > static_cast<int32_t>(MG_TF_STEPS_MASK))
+    bad = "timeout_steps must be in 1..8191 (the step count of mg_state.tf saturates at 8191)";
+  else if (!(p->R > 0.0 && p->R < HUGE_VAL)) bad = "R must be positive and finite";
+  else if (!(p->dT > 0.0 && p->dT < HUGE_VAL)) bad = "dT must be positive and finite";
+  else if (p->veh_w <= 0) bad = "veh_w must be positive";
+  else if (p->veh_h <= 0) bad = "veh_h must be positive";
+  else if (!(p->inv_R == 1.0 / p->R)) bad = "inv_R must be 1 / R, rounded";
+  else if (!(p->qp_inv_nz == 1.0 / p->qp_nz)) bad = "qp_inv_nz must be 1 / qp_nz, rounded";
+  return bad ? fail(hipErrorInvalidValue, "mg_params: %s", bad) : 0;
+}
+
+int check_common(const mg_params* p, const mg_state* s, const mg_outputs* o, int64_t n) {
+  if (int e = check_params(p)) return e;
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (n > (static_cast<int64_t>(0x7fffffff) * kBlock))
     return fail(hipErrorInvalidValue, "%s", "n exceeds the grid limit");

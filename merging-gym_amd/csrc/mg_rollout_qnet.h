@@ -52,9 +52,12 @@ struct FinishBound {
 // Rect truncation of vehicle_box). A step moves a car by dl <= dT vmax along its arc, vmax =
 // max(start_vel, action speeds) + 0.5 (a speed only moves toward an action's target), and so its
 // lateral y by at most dl |sin theta|; where y1 - y2 < lat the ego's 1 - cos theta < lat / R, so
-// |sin theta| < sqrt(2 lat / R) + dl / R over the step. lat = veh_w + 1 + max(0.75, 2 dl sin + 0.25):
-// the default params' 0.75 (5.75) stands unless the geometry needs more. The longitudinal reach of
-// the speeds is added at run time (rel in may_finish_next).
+// |sin theta| < min(1, sqrt(2 lat / R) + dl / R) over the step. lat = veh_w + 1 + max(0.75, 2 dl sin + 0.25):
+// the default params' 0.75 (5.75) stands unless the geometry needs more. lat appears in its own bound,
+// and the bound grows with lat, so the passes climb from below until lat stops changing: the least
+// fixed point, which satisfies the inequality (a fixed number of passes stops under it). |sin| <= 1
+// caps it at veh_w + 1.25 + 2 dl. Rounded up to fp32. The longitudinal reach of the speeds is added
+// at run time (rel in may_finish_next).
 inline FinishBound finish_bound(const mg_params& P) {
   double smin = P.action_speed[0], smax = smin;
   for (int a = 1; a < MG_NUM_ACTIONS; ++a) {
@@ -63,14 +66,19 @@ inline FinishBound finish_bound(const mg_params& P) {
   }
   const double vmax = std::max(smax, P.start_vel) + 0.5;
   const double dl = P.dT * vmax;
+  const double cap = P.veh_w + 1.25 + 2.0 * dl;
   double lat = P.veh_w + 1.75;
-  for (int it = 0; it < 4; ++it) {  // lat appears in its own bound: a few fixed-point passes
-    const double sn = std::sqrt(2.0 * lat / P.R) + dl / P.R;
-    lat = P.veh_w + 1.0 + std::max(0.75, 2.0 * dl * sn + 0.25);
+  for (int it = 0; it < 4096; ++it) {  // monotone from below and bounded by cap: ends at the fixed point
+    const double sn = std::min(1.0, std::sqrt(2.0 * lat / P.R) + dl / P.R);
+    const double next = std::min(cap, P.veh_w + 1.0 + std::max(0.75, 2.0 * dl * sn + 0.25));
+    if (!(next > lat)) break;
+    lat = next;
   }
+  float latf = static_cast<float>(lat);
+  if (latf < lat) latf = std::nextafterf(latf, INFINITY);
   // rounded outward by a margin: the bound only has to contain every speed a step reaches
   return FinishBound{static_cast<float>(smin) - 0.5f, static_cast<float>(smax) + 0.5f,
-                     static_cast<float>(P.dT * P.qp_z0 / P.qp_nz) * 1.01f, static_cast<float>(lat),
+                     static_cast<float>(P.dT * P.qp_z0 / P.qp_nz) * 1.01f, latf,
                      static_cast<float>(P.veh_h + 1)};
 }
 struct QRollout {

@@ -80,18 +80,26 @@ class QNet:
         can go stale when `packed` changes."""
         return self.packed
 
-    def reset_argmax(self) -> int:
+    def reset_argmax(self, params=None) -> int:
         """argmax of this net on the reset observation (merging_env.py:208-230), computed once on
         the device: the greedy goal Goal_DQN picks after every episode end (hdqn.py:278-283),
-        which mg_rollout_hdqn takes as a constant."""
-        if getattr(self, "_reset_argmax", None) is None:
+        which mg_rollout_hdqn takes as a constant. params: the env's mg_params (the reset
+        observation follows start_point, start_vel, R, H, W and end_point); None = the defaults.
+        One value is kept per distinct params."""
+        import ctypes
+
+        key = None if params is None else bytes(params)
+        cache = self.__dict__.setdefault("_reset_argmax", {})
+        if key not in cache:
             from .envs.vector_env import MergeVecEnv
 
             if self.in_dim != 10:
                 raise ValueError("reset_argmax needs a net on the 10-value observation")
             one = MergeVecEnv(1, device=self.device, final_observation=False, episode_stats=False)
-            self._reset_argmax = int(self.forward(one.reset())[0].argmax())
-        return self._reset_argmax
+            if params is not None:
+                ctypes.memmove(ctypes.byref(one.params), ctypes.byref(params), ctypes.sizeof(params))
+            cache[key] = int(self.forward(one.reset())[0].argmax())
+        return cache[key]
 
     @classmethod
     def from_state_dict(cls, sd, device=None):

@@ -39,28 +39,38 @@ typedef struct oracle_env {
   int32_t pad_;
 } oracle_env;
 
-/* merging_env.py:22-46, :101 */
-static const double R = 30000.0, H = 1000.0, W = 300.0, DT = 0.2;
-static const double R_FIRST = 2.0, R_SECOND = 1.0, R_COLLISION = -10.0;
-static const double VEL_PENALTY = 0.001, TIME_PENALTY = 0.0;
-static const double START_POINT = 50.0, END_POINT = 950.0, PREDICTION_T = 3.0;
-static const int VEHICLE_W = 4, VEHICLE_H = 8;
-static const double ACTION_SPEED[5] = {0.0, 10.0, 20.0, 30.0, 40.0};
+/* The reference's module-level constants (merging_env.py:22-46), its action_dict (:101) and the three
+ * numbers it writes as literals: the reset speed (:216-217), the reward's reference speed (:158-159)
+ * and the time limit (:142). Parameters travel per call (the *_p entry points); the entry points
+ * without them pass ORACLE_DEFAULTS. Mirrored by OracleParamsC in merge_oracle.py. */
+typedef struct oracle_params {
+  double R, H, W, dT;
+  double r_first, r_second, r_collision;
+  double vel_penalty, time_penalty;
+  double start_point, end_point, prediction_t;
+  double start_vel, vel_ref, time_limit;
+  double action_speed[5];
+  int32_t veh_w, veh_h;
+} oracle_params;
+
+static const oracle_params ORACLE_DEFAULTS = {
+    30000.0, 1000.0, 300.0, 0.2, 2.0, 1.0, -10.0, 0.001, 0.0, 50.0, 950.0, 3.0, 20.0, 20.0, 500.0,
+    {0.0, 10.0, 20.0, 30.0, 40.0}, 4, 8};
 
 /* status bits, identical to include/merging_hip.h MG_ST_* */
 enum { ST_DONE = 1, ST_COLL = 2, ST_R1_INT = 4, ST_R2_INT = 8, ST_V1_INT = 16, ST_V2_INT = 32,
        ST_ERR1 = 64, ST_ERR2 = 128 };
 
-static double arc_angle(double lon) {
-  volatile double h = H, r = R; /* evaluate atan2 at run time, as numpy does */
-  return atan2(h, r) - lon / R;
+static double arc_angle(const oracle_params* p, double lon) {
+  volatile double h = p->H, r = p->R; /* evaluate atan2 at run time, as numpy does */
+  return atan2(h, r) - lon / p->R;
 }
 
-static void lon2coord(double lon, int ego, double* x, double* y) {
-  const double a = arc_angle(lon);
-  *x = R * sin(a);
-  const double bulge = R - R * cos(a);
-  *y = ego ? W / 2 + bulge : W / 2 - bulge;
+static void lon2coord(const oracle_params* p, double lon, int ego, double* x, double* y) {
+  const double a = arc_angle(p, lon);
+  *x = p->R * sin(a);
+  const double bulge = p->R - p->R * cos(a);
+  *y = ego ? p->W / 2 + bulge : p->W / 2 - bulge;
 }
 
 /* quadprog 0.1.11's qpgen2 (helper.py:182 -> qpsolvers 1.8.0 quadprog_solve_qp: G = P, a = -q = 0,
@@ -184,11 +194,11 @@ static double mpc_first_accel(double x0, double v0, double xt, double vt, double
 /* corners(agent, y=x, x=y, 0) (merging_env.py:232-239) as a closed box */
 typedef struct { double xmin, xmax, ymin, ymax; } box;
 
-static box vehicle_box(double lateral, double longitudinal) {
-  const int left = (int)lateral - VEHICLE_W / 2; /* pygame Rect: C (int) cast of the centre */
-  const int top = (int)longitudinal - VEHICLE_H / 2;
-  const double c[4][2] = {{left, top}, {left + VEHICLE_W, top},
-                          {left + VEHICLE_W, top + VEHICLE_H}, {left, top + VEHICLE_H}};
+static box vehicle_box(const oracle_params* p, double lateral, double longitudinal) {
+  const int left = (int)lateral - p->veh_w / 2; /* pygame Rect: C (int) cast of the centre */
+  const int top = (int)longitudinal - p->veh_h / 2;
+  const double c[4][2] = {{left, top}, {left + p->veh_w, top},
+                          {left + p->veh_w, top + p->veh_h}, {left, top + p->veh_h}};
   box b = {INFINITY, -INFINITY, INFINITY, -INFINITY};
   for (int k = 0; k < 4; ++k) {
     /* scale * (Vector2(corner) - pivot).rotate(-0) + pivot, scale = 1.0 */
@@ -206,41 +216,43 @@ static int polygons_intersect(box a, box b) { /* closed sets: touching counts */
   return a.xmin <= b.xmax && b.xmin <= a.xmax && a.ymin <= b.ymax && b.ymin <= a.ymax;
 }
 
-static int is_collided(const oracle_env* e) {
+static int is_collided(const oracle_params* p, const oracle_env* e) {
   double x1, y1, x2, y2;
-  lon2coord(e->pos1, 1, &x1, &y1);
-  lon2coord(e->pos2, 0, &x2, &y2);
-  return polygons_intersect(vehicle_box(y1, x1), vehicle_box(y2, x2));
+  lon2coord(p, e->pos1, 1, &x1, &y1);
+  lon2coord(p, e->pos2, 0, &x2, &y2);
+  return polygons_intersect(vehicle_box(p, y1, x1), vehicle_box(p, y2, x2));
 }
 
-static void observe(const oracle_env* e, double o[10]) {
+static void observe(const oracle_params* p, const oracle_env* e, double o[10]) {
   double x1, y1, x2, y2;
-  lon2coord(e->pos1, 1, &x1, &y1);
-  lon2coord(e->pos2, 0, &x2, &y2);
-  o[0] = x2 - x1; o[1] = y2 - y1; o[2] = e->vel2 - e->vel1; o[3] = END_POINT - e->pos1;
+  lon2coord(p, e->pos1, 1, &x1, &y1);
+  lon2coord(p, e->pos2, 0, &x2, &y2);
+  o[0] = x2 - x1; o[1] = y2 - y1; o[2] = e->vel2 - e->vel1; o[3] = p->end_point - e->pos1;
   o[4] = e->vel1; o[5] = x1 - x2; o[6] = y1 - y2; o[7] = e->vel1 - e->vel2;
-  o[8] = END_POINT - e->pos2; o[9] = e->vel2;
+  o[8] = p->end_point - e->pos2; o[9] = e->vel2;
 }
 
-static void env_reset(oracle_env* e, double o[10]) {
+static void env_reset(const oracle_params* p, oracle_env* e, double o[10]) {
   memset(e, 0, sizeof(*e));
-  e->pos1 = e->pos2 = START_POINT;
-  e->vel1 = e->vel2 = 20.0;
-  if (o) observe(e, o);
+  e->pos1 = e->pos2 = p->start_point;
+  e->vel1 = e->vel2 = p->start_vel;
+  if (o) observe(p, e, o);
 }
 
 static int valid(int a) { return a >= 0 && a < 5; }
 
 /* one MergeEnv.step; a2 < 0 means None. Returns ST_* bits. */
-static uint32_t env_step(oracle_env* e, int a1, int a2, double o[10], double rew[2], int* coll) {
+static uint32_t env_step(const oracle_params* p, oracle_env* e, int a1, int a2, double o[10], double rew[2],
+                         int* coll) {
+  const double DT = p->dT, PREDICTION_T = p->prediction_t, END_POINT = p->end_point;
   uint32_t st = 0;
   e->time_stamp += DT;
   e->steps += 1;
-  if (e->time_stamp > 500) e->done = 1;
+  if (e->time_stamp > p->time_limit) e->done = 1;
   *coll = 0;
   if (!valid(a1)) return ST_ERR1;
   {
-    const double vt = ACTION_SPEED[a1];
+    const double vt = p->action_speed[a1];
     e->acc1 = mpc_first_accel(e->pos1, e->vel1, e->pos1 + vt * PREDICTION_T, vt, PREDICTION_T);
     const double v = e->vel1 + e->acc1 * DT;
     if (v > 0) e->vel1 = v; else { e->vel1 = 0.0; st |= ST_V1_INT; } /* max(0, v) */
@@ -250,7 +262,7 @@ static uint32_t env_step(oracle_env* e, int a1, int a2, double o[10], double rew
   if (a2 < 0) {
     e->acc2 = 0.0;
   } else {
-    const double vt = ACTION_SPEED[a2];
+    const double vt = p->action_speed[a2];
     e->acc2 = mpc_first_accel(e->pos2, e->vel2, e->pos2 + vt * PREDICTION_T, vt, PREDICTION_T);
   }
   {
@@ -258,23 +270,23 @@ static uint32_t env_step(oracle_env* e, int a1, int a2, double o[10], double rew
     if (v > 0) e->vel2 = v; else { e->vel2 = 0.0; st |= ST_V2_INT; }
     e->pos2 += e->vel2 * DT;
   }
-  observe(e, o);
-  double r1 = (0.0 - TIME_PENALTY) - VEL_PENALTY * fabs(e->vel1 - 20.0);
-  double r2 = (0.0 - TIME_PENALTY) - VEL_PENALTY * fabs(e->vel2 - 20.0);
+  observe(p, e, o);
+  double r1 = (0.0 - p->time_penalty) - p->vel_penalty * fabs(e->vel1 - p->vel_ref);
+  double r2 = (0.0 - p->time_penalty) - p->vel_penalty * fabs(e->vel2 - p->vel_ref);
   if (e->pos1 > END_POINT) {
-    if (e->winner == 0) { e->winner = 1; r1 += R_FIRST; }
+    if (e->winner == 0) { e->winner = 1; r1 += p->r_first; }
     else if (e->winner == 1) { r1 = 0.0; st |= ST_R1_INT; }
-    else { r1 += R_SECOND; e->done = 1; }
+    else { r1 += p->r_second; e->done = 1; }
   }
   if (e->pos2 >= END_POINT) {
-    if (e->winner == 0) { e->winner = 2; r2 += R_FIRST; }
+    if (e->winner == 0) { e->winner = 2; r2 += p->r_first; }
     else if (e->winner == 2) { r2 = 0.0; st |= ST_R2_INT; }
-    else { r2 += R_SECOND; e->done = 1; }
+    else { r2 += p->r_second; e->done = 1; }
   }
-  if (is_collided(e)) {
+  if (is_collided(p, e)) {
     e->done = 1;
-    r1 += R_COLLISION;
-    r2 += R_COLLISION;
+    r1 += p->r_collision;
+    r2 += p->r_collision;
     *coll = 1;
     st |= ST_COLL;
   }
@@ -296,8 +308,8 @@ static uint32_t env_step(oracle_env* e, int a1, int a2, double o[10], double rew
  *   hdqn.py:342     the same test on the terminal observation.
  * ret_sum[3] = (sum r1_accumulate, sum r2_accumulate, sum main.py ep_reward); counts[6] =
  * (episodes, collisions, winner == 1, steps, main.py wins, hdqn.py wins). */
-static int win_test(const oracle_env* e) { /* state[8] > state[3] of observe() */
-  return (END_POINT - e->pos2) > (END_POINT - e->pos1);
+static int win_test(const oracle_params* p, const oracle_env* e) { /* state[8] > state[3] of observe() */
+  return (p->end_point - e->pos2) > (p->end_point - e->pos1);
 }
 
 static void oracle_note_step(oracle_env* e, const double rew[2]) {
@@ -305,8 +317,8 @@ static void oracle_note_step(oracle_env* e, const double rew[2]) {
 }
 
 /* Episode bookkeeping + gym.vector autoreset (obs <- reset obs, fobs <- terminal obs). */
-static void finish_episode(oracle_env* e, int coll, int win_pre, double* o, double* fobs, double* ret_sum,
-                           uint32_t* counts) {
+static void finish_episode(const oracle_params* p, oracle_env* e, int coll, int win_pre, double* o, double* fobs,
+                           double* ret_sum, uint32_t* counts) {
   if (ret_sum) {
     ret_sum[0] += e->r1_acc;
     ret_sum[1] += e->r2_acc;
@@ -318,10 +330,10 @@ static void finish_episode(oracle_env* e, int coll, int win_pre, double* o, doub
     counts[2] += e->winner == 1 ? 1u : 0u;
     counts[3] += (uint32_t)e->steps;
     counts[4] += win_pre ? 1u : 0u;
-    counts[5] += win_test(e) ? 1u : 0u;
+    counts[5] += win_test(p, e) ? 1u : 0u;
   }
   if (fobs) memcpy(fobs, o, 10 * sizeof(double));
-  env_reset(e, o);
+  env_reset(p, e, o);
 }
 
 /* ------------------------------------------------------------------ Philox4x32-10 */
@@ -329,6 +341,15 @@ static void finish_episode(oracle_env* e, int coll, int win_pre, double* o, doub
 double oracle_mpc_first_accel(double x0, double v0, double xt, double vt, double t) {
   return mpc_first_accel(x0, v0, xt, vt, t);
 }
+
+/* action_to_acc (merging_env.py:134-136, :147) for action a from (x0, v0) under *p */
+double oracle_mpc_first_accel_p(const oracle_params* p, double x0, double v0, int32_t a) {
+  const double vt = p->action_speed[a];
+  return mpc_first_accel(x0, v0, x0 + vt * p->prediction_t, vt, p->prediction_t);
+}
+
+/* the size of oracle_params, for the binding's layout check */
+int32_t oracle_params_size(void) { return (int32_t)sizeof(oracle_params); }
 
 void oracle_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
   uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
@@ -394,34 +415,46 @@ int32_t oracle_max_threads(void) {
 }
 
 /* observe() (merging_env.py:118-132) of n envs, no state change: obs[n,10] f64 */
+void oracle_observe_batch_p(const oracle_params* p, const oracle_env* envs, int64_t n, double* obs) {
+  for (int64_t i = 0; i < n; ++i) observe(p, &envs[i], obs + 10 * i);
+}
+
 void oracle_observe_batch(const oracle_env* envs, int64_t n, double* obs) {
-  for (int64_t i = 0; i < n; ++i) observe(&envs[i], obs + 10 * i);
+  oracle_observe_batch_p(&ORACLE_DEFAULTS, envs, n, obs);
+}
+
+void oracle_reset_batch_p(const oracle_params* p, oracle_env* envs, int64_t n, double* obs) {
+  for (int64_t i = 0; i < n; ++i) env_reset(p, &envs[i], obs ? obs + 10 * i : NULL);
 }
 
 void oracle_reset_batch(oracle_env* envs, int64_t n, double* obs) {
-  for (int64_t i = 0; i < n; ++i) env_reset(&envs[i], obs ? obs + 10 * i : NULL);
+  oracle_reset_batch_p(&ORACLE_DEFAULTS, envs, n, obs);
+}
+
+/* is_collided (merging_env.py:198-206) of n envs, no state change */
+void oracle_collided_batch_p(const oracle_params* p, const oracle_env* envs, int64_t n, uint8_t* coll) {
+  for (int64_t i = 0; i < n; ++i) coll[i] = (uint8_t)is_collided(p, &envs[i]);
 }
 
 /* One step of n envs. a2 may be NULL (all None). Returns OR of the error bits (1: a1, 2: a2). */
-int32_t oracle_step_batch(oracle_env* envs, int64_t n, const int8_t* a1, const int8_t* a2,
-                          int32_t autoreset, double* obs, double* rew, uint8_t* done,
-                          uint8_t* coll, double* final_obs, double* ret_sum, uint32_t* counts,
-                          uint32_t* status, int32_t unused) {
-  (void)unused;
+int32_t oracle_step_batch_p(const oracle_params* p, oracle_env* envs, int64_t n, const int8_t* a1,
+                            const int8_t* a2, int32_t autoreset, double* obs, double* rew, uint8_t* done,
+                            uint8_t* coll, double* final_obs, double* ret_sum, uint32_t* counts,
+                            uint32_t* status) {
   int32_t err = 0;
 #pragma omp parallel for schedule(static) reduction(| : err)
   for (int64_t i = 0; i < n; ++i) {
     double o[10] = {0}, r[2] = {0, 0};
     int c = 0;
-    const int win_pre = win_test(&envs[i]);
-    const uint32_t st = env_step(&envs[i], a1[i], a2 ? a2[i] : -1, o, r, &c);
+    const int win_pre = win_test(p, &envs[i]);
+    const uint32_t st = env_step(p, &envs[i], a1[i], a2 ? a2[i] : -1, o, r, &c);
     if (st & ST_ERR1) err |= 1;
     if (st & ST_ERR2) err |= 2;
     const int bad = (st & (ST_ERR1 | ST_ERR2)) != 0;
     if (!bad) oracle_note_step(&envs[i], r);
     const int d = bad ? 0 : envs[i].done;
     if (autoreset && d)
-      finish_episode(&envs[i], c, win_pre, o, final_obs ? final_obs + 10 * i : NULL,
+      finish_episode(p, &envs[i], c, win_pre, o, final_obs ? final_obs + 10 * i : NULL,
                      ret_sum ? ret_sum + 3 * i : NULL, counts ? counts + 6 * i : NULL);
     if (obs) memcpy(obs + 10 * i, o, sizeof(o));
     if (rew) { rew[2 * i] = r[0]; rew[2 * i + 1] = r[1]; }
@@ -432,25 +465,41 @@ int32_t oracle_step_batch(oracle_env* envs, int64_t n, const int8_t* a1, const i
   return err;
 }
 
+int32_t oracle_step_batch(oracle_env* envs, int64_t n, const int8_t* a1, const int8_t* a2,
+                          int32_t autoreset, double* obs, double* rew, uint8_t* done,
+                          uint8_t* coll, double* final_obs, double* ret_sum, uint32_t* counts,
+                          uint32_t* status, int32_t unused) {
+  (void)unused;
+  return oracle_step_batch_p(&ORACLE_DEFAULTS, envs, n, a1, a2, autoreset, obs, rew, done, coll, final_obs,
+                             ret_sum, counts, status);
+}
+
 /* `steps` autoreset steps with Philox actions: the CPU baseline of the bench workload. */
-int64_t oracle_rollout_random(oracle_env* envs, int64_t n, int64_t steps, uint64_t seed,
-                              uint64_t first_step, int32_t opp_random, int64_t env_offset,
-                              double* ret_sum, uint32_t* counts) {
+int64_t oracle_rollout_random_p(const oracle_params* p, oracle_env* envs, int64_t n, int64_t steps,
+                                uint64_t seed, uint64_t first_step, int32_t opp_random, int64_t env_offset,
+                                double* ret_sum, uint32_t* counts) {
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < n; ++i) {
     for (int64_t k = 0; k < steps; ++k) {
       int x, y, c = 0;
       double o[10], r[2];
       draw_actions(env_offset + i, seed, first_step + (uint64_t)k, opp_random, &x, &y);
-      const int win_pre = win_test(&envs[i]);
-      env_step(&envs[i], x, y, o, r, &c);
+      const int win_pre = win_test(p, &envs[i]);
+      env_step(p, &envs[i], x, y, o, r, &c);
       oracle_note_step(&envs[i], r);
       if (envs[i].done)
-        finish_episode(&envs[i], c, win_pre, o, NULL, ret_sum ? ret_sum + 3 * i : NULL,
+        finish_episode(p, &envs[i], c, win_pre, o, NULL, ret_sum ? ret_sum + 3 * i : NULL,
                        counts ? counts + 6 * i : NULL);
     }
   }
   return n * steps;
+}
+
+int64_t oracle_rollout_random(oracle_env* envs, int64_t n, int64_t steps, uint64_t seed,
+                              uint64_t first_step, int32_t opp_random, int64_t env_offset,
+                              double* ret_sum, uint32_t* counts) {
+  return oracle_rollout_random_p(&ORACLE_DEFAULTS, envs, n, steps, seed, first_step, opp_random, env_offset,
+                                 ret_sum, counts);
 }
 
 /* The four Philox words of (env_offset + i, step) for i < n: out[4 i + 0..3]. */

@@ -25,6 +25,7 @@ through the reference's call sites ("Oracle").
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import os
 import subprocess
@@ -43,12 +44,83 @@ PREDICTION_T = 3.0
 ACTION_SPEED = {0: 0, 1: 10, 2: 20, 3: 30, 4: 40}
 
 
-def arc_position(lon, ego: bool):
+@dataclasses.dataclass(frozen=True)
+class OracleParams:
+    """The reference's module-level constants (merging_env.py:22-46), its action_dict (:101) and the
+    three numbers it writes as literals: the reset speed start_vel (:216-217), the reward's reference
+    speed vel_ref (:158-159) and the time limit (:142, `time_stamp += dT; time_stamp > limit` on the
+    fp64 clock). Values keep the Python type they are given (the reference's ints stay ints, so an
+    observation after reset holds the int END_POINT - START_POINT). Parameters travel per call:
+    PyMergeEnv(params) and the params= argument of COracle's methods; None is DEFAULT_PARAMS."""
+
+    R: float = R
+    H: float = H
+    W: float = W
+    dT: float = DT
+    RFirst: float = R_FIRST
+    RSecond: float = R_SECOND
+    RCollision: float = R_COLLISION
+    vel_penalty: float = VEL_PENALTY
+    time_penalty: float = TIME_PENALTY
+    START_POINT: float = START_POINT
+    END_POINT: float = END_POINT
+    VEHICLE_W: int = VEHICLE_W
+    VEHICLE_H: int = VEHICLE_H
+    prediction_t: float = PREDICTION_T
+    action_speeds: tuple = tuple(ACTION_SPEED[a] for a in range(5))
+    start_vel: float = 20.0
+    vel_ref: float = 20.0
+    time_limit: float = 500
+
+    def timeout_steps(self) -> int:
+        """The first step whose clock exceeds the limit: the number of sequential fp64 additions of
+        dT (from the int 0 of reset) after which time_stamp > time_limit."""
+        t, k = 0, 0
+        while not t > self.time_limit:
+            t += self.dT
+            k += 1
+        return k
+
+    def clock(self, steps):
+        """time_stamp after `steps` steps (array or int): the same sequential fp64 sum."""
+        steps = np.asarray(steps)
+        top = int(steps.max()) if steps.size else 0
+        ts = np.concatenate([[0.0], np.cumsum(np.full(top, float(self.dT)))])
+        return ts[steps]
+
+    def as_c(self) -> "OracleParamsC":
+        c = OracleParamsC()
+        for cname, name in _C_PARAM_FIELDS:
+            setattr(c, cname, float(getattr(self, name)))
+        c.action_speed = (ctypes.c_double * 5)(*[float(v) for v in self.action_speeds])
+        c.veh_w, c.veh_h = int(self.VEHICLE_W), int(self.VEHICLE_H)
+        return c
+
+
+_C_PARAM_FIELDS = (("R", "R"), ("H", "H"), ("W", "W"), ("dT", "dT"), ("r_first", "RFirst"),
+                   ("r_second", "RSecond"), ("r_collision", "RCollision"), ("vel_penalty", "vel_penalty"),
+                   ("time_penalty", "time_penalty"), ("start_point", "START_POINT"),
+                   ("end_point", "END_POINT"), ("prediction_t", "prediction_t"), ("start_vel", "start_vel"),
+                   ("vel_ref", "vel_ref"), ("time_limit", "time_limit"))
+
+
+class OracleParamsC(ctypes.Structure):
+    """struct oracle_params in merge_oracle.c."""
+
+    _fields_ = [(c, ctypes.c_double) for c, _ in _C_PARAM_FIELDS] + [
+        ("action_speed", ctypes.c_double * 5), ("veh_w", ctypes.c_int32), ("veh_h", ctypes.c_int32)]
+
+
+DEFAULT_PARAMS = OracleParams()
+
+
+def arc_position(lon, ego: bool, params: OracleParams | None = None):
     """lon2coord (merging_env.py:48-58): longitudinal x and lateral y on the mirrored arcs."""
-    theta = np.arctan2(H, R) - lon / R
-    x = R * np.sin(theta)
-    bulge = R - R * np.cos(theta)
-    return x, (W / 2 + bulge) if ego else (W / 2 - bulge)
+    p = params or DEFAULT_PARAMS
+    theta = np.arctan2(p.H, p.R) - lon / p.R
+    x = p.R * np.sin(theta)
+    bulge = p.R - p.R * np.cos(theta)
+    return x, (p.W / 2 + bulge) if ego else (p.W / 2 - bulge)
 
 
 _QP_CACHE = {}
@@ -146,7 +218,7 @@ def first_accel(x0, v0, xt, vt, t):
     return sol0 + tt * (sign * z[0])
 
 
-def vehicle_box(lateral, longitudinal):
+def vehicle_box(lateral, longitudinal, params: OracleParams | None = None):
     """corners(agent, y=x, x=y, 0) (merging_env.py:232-239) as a closed box.
 
     pygame's Rect(center=(lateral, longitudinal)) truncates the float centre with a C (int)
@@ -154,10 +226,11 @@ def vehicle_box(lateral, longitudinal):
     surfaces are make_surface(ones([4, 8])), :97-98). Each Vector2 corner is
     (corner - pivot).rotate(0) * 1.0 + pivot in fp64.
     """
-    left = int(lateral) - VEHICLE_W // 2
-    top = int(longitudinal) - VEHICLE_H // 2
-    xs = [(float(c) - lateral) + lateral for c in (left, left + VEHICLE_W)]
-    ys = [(float(c) - longitudinal) + longitudinal for c in (top, top + VEHICLE_H)]
+    p = params or DEFAULT_PARAMS
+    left = int(lateral) - p.VEHICLE_W // 2
+    top = int(longitudinal) - p.VEHICLE_H // 2
+    xs = [(float(c) - lateral) + lateral for c in (left, left + p.VEHICLE_W)]
+    ys = [(float(c) - longitudinal) + longitudinal for c in (top, top + p.VEHICLE_H)]
     return min(xs), max(xs), min(ys), max(ys)
 
 
@@ -169,75 +242,81 @@ def boxes_touch(b1, b2) -> bool:
 class PyMergeEnv:
     """Scalar restatement of MergeEnv's step/reset path with the reference's list API."""
 
-    def __init__(self):
+    def __init__(self, params: OracleParams | None = None):
+        self.params = params or DEFAULT_PARAMS
+        self.action_dict = dict(enumerate(self.params.action_speeds))
         self.reset()
 
     def reset(self):
         # merging_env.py:208-230 (deterministic start; the random start is commented out)
+        p = self.params
         self.done = False
         self.winner = None
         self.time_stamp = 0
-        self.state1 = {"pos": START_POINT, "vel": 20.0, "acc": 0.0}
-        self.state2 = {"pos": START_POINT, "vel": 20.0, "acc": 0.0}
+        self.state1 = {"pos": p.START_POINT, "vel": p.start_vel, "acc": 0.0}
+        self.state2 = {"pos": p.START_POINT, "vel": p.start_vel, "acc": 0.0}
         self.r1_accumulate = 0
         self.r2_accumulate = 0
         return self.observe()
 
     def observe(self):
-        x1, y1 = arc_position(self.state1["pos"], True)
-        x2, y2 = arc_position(self.state2["pos"], False)
+        p = self.params
+        x1, y1 = arc_position(self.state1["pos"], True, p)
+        x2, y2 = arc_position(self.state2["pos"], False, p)
         s1, s2 = self.state1, self.state2
-        return [x2 - x1, y2 - y1, s2["vel"] - s1["vel"], END_POINT - s1["pos"], s1["vel"],
-                x1 - x2, y1 - y2, s1["vel"] - s2["vel"], END_POINT - s2["pos"], s2["vel"]]
+        return [x2 - x1, y2 - y1, s2["vel"] - s1["vel"], p.END_POINT - s1["pos"], s1["vel"],
+                x1 - x2, y1 - y2, s1["vel"] - s2["vel"], p.END_POINT - s2["pos"], s2["vel"]]
 
-    @staticmethod
-    def _advance(car, action):
-        vt = ACTION_SPEED[action]  # KeyError for an invalid action, as the reference
-        car["acc"] = first_accel(car["pos"], car["vel"], car["pos"] + vt * PREDICTION_T, vt,
-                                 PREDICTION_T)
-        car["vel"] = max(0, car["vel"] + car["acc"] * DT)
-        car["pos"] += car["vel"] * DT
+    def _advance(self, car, action):
+        p = self.params
+        vt = self.action_dict[action]  # KeyError for an invalid action, as the reference
+        car["acc"] = first_accel(car["pos"], car["vel"], car["pos"] + vt * p.prediction_t, vt,
+                                 p.prediction_t)
+        car["vel"] = max(0, car["vel"] + car["acc"] * p.dT)
+        car["pos"] += car["vel"] * p.dT
 
     def collided(self):
-        x1, y1 = arc_position(self.state1["pos"], True)
-        x2, y2 = arc_position(self.state2["pos"], False)
-        return boxes_touch(vehicle_box(y1, x1), vehicle_box(y2, x2))
+        p = self.params
+        x1, y1 = arc_position(self.state1["pos"], True, p)
+        x2, y2 = arc_position(self.state2["pos"], False, p)
+        return boxes_touch(vehicle_box(y1, x1, p), vehicle_box(y2, x2, p))
 
     def step(self, action1, action2=None):
         # merging_env.py:138-195
-        self.time_stamp += DT
-        if self.time_stamp > 500:
+        p = self.params
+        self.time_stamp += p.dT
+        if self.time_stamp > p.time_limit:
             self.done = True
         info = {"collision": False}
         self._advance(self.state1, action1)
         if action2 is None:
             self.state2["acc"] = 0
-            self.state2["vel"] = max(0, self.state2["vel"] + 0 * DT)
-            self.state2["pos"] += self.state2["vel"] * DT
+            self.state2["vel"] = max(0, self.state2["vel"] + 0 * p.dT)
+            self.state2["pos"] += self.state2["vel"] * p.dT
         else:
             self._advance(self.state2, action2)
         obs = self.observe()
-        r1 = -TIME_PENALTY - VEL_PENALTY * np.abs(self.state1["vel"] - 20.0)
-        r2 = -TIME_PENALTY - VEL_PENALTY * np.abs(self.state2["vel"] - 20.0)
+        r1 = -p.time_penalty - p.vel_penalty * np.abs(self.state1["vel"] - p.vel_ref)
+        r2 = -p.time_penalty - p.vel_penalty * np.abs(self.state2["vel"] - p.vel_ref)
         # arrival: ego strict, opponent non-strict; the first arrival wins
-        if self.state1["pos"] > END_POINT:
+        if self.state1["pos"] > p.END_POINT:
             if self.winner is None:
-                self.winner, r1 = 1, r1 + R_FIRST
+                self.winner, r1 = 1, r1 + p.RFirst
             elif self.winner == 1:
                 r1 = 0
             else:
-                r1, self.done = r1 + R_SECOND, True
-        if self.state2["pos"] >= END_POINT:
+                r1, self.done = r1 + p.RSecond, True
+        if self.state2["pos"] >= p.END_POINT:
             if self.winner is None:
-                self.winner, r2 = 2, r2 + R_FIRST
+                self.winner, r2 = 2, r2 + p.RFirst
             elif self.winner == 2:
                 r2 = 0
             else:
-                r2, self.done = r2 + R_SECOND, True
+                r2, self.done = r2 + p.RSecond, True
         if self.collided():
             self.done = True
-            r1 += R_COLLISION
-            r2 += R_COLLISION
+            r1 += p.RCollision
+            r2 += p.RCollision
             info["collision"] = True
         # np.float64 -> float so the list holds plain Python numbers like the reference's
         r1 = r1 if isinstance(r1, int) else float(r1)
@@ -324,6 +403,19 @@ class COracle:
                                             P(ctypes.c_uint32)]
         lib.oracle_mpc_first_accel.argtypes = [ctypes.c_double] * 5
         lib.oracle_mpc_first_accel.restype = ctypes.c_double
+        PP = P(OracleParamsC)
+        lib.oracle_reset_batch_p.argtypes = [PP] + lib.oracle_reset_batch.argtypes
+        lib.oracle_observe_batch_p.argtypes = [PP] + lib.oracle_observe_batch.argtypes
+        lib.oracle_collided_batch_p.argtypes = [PP, ctypes.c_void_p, ctypes.c_int64, P(ctypes.c_uint8)]
+        lib.oracle_step_batch_p.argtypes = [PP] + lib.oracle_step_batch.argtypes[:-1]
+        lib.oracle_step_batch_p.restype = ctypes.c_int32
+        lib.oracle_rollout_random_p.argtypes = [PP] + lib.oracle_rollout_random.argtypes
+        lib.oracle_rollout_random_p.restype = ctypes.c_int64
+        lib.oracle_mpc_first_accel_p.argtypes = [PP, ctypes.c_double, ctypes.c_double, ctypes.c_int32]
+        lib.oracle_mpc_first_accel_p.restype = ctypes.c_double
+        lib.oracle_params_size.restype = ctypes.c_int32
+        if lib.oracle_params_size() != ctypes.sizeof(OracleParamsC):
+            raise ImportError("oracle_params layout differs between merge_oracle.c and merge_oracle.py")
         lib.oracle_set_threads.argtypes = [ctypes.c_int32]
         lib.oracle_max_threads.restype = ctypes.c_int32
         self.lib = lib
@@ -338,18 +430,33 @@ class COracle:
     def new_envs(n: int) -> np.ndarray:
         return np.zeros(n, dtype=ENV_DTYPE)
 
-    def observe(self, envs: np.ndarray) -> np.ndarray:
+    def observe(self, envs: np.ndarray, params: OracleParams | None = None) -> np.ndarray:
         """observe() (merging_env.py:118-132) of every env in fp64, no state change."""
         obs = np.empty((len(envs), 10), np.float64)
-        self.lib.oracle_observe_batch(envs.ctypes.data, len(envs), _ptr(obs, ctypes.c_double))
+        if params is None:
+            self.lib.oracle_observe_batch(envs.ctypes.data, len(envs), _ptr(obs, ctypes.c_double))
+        else:
+            self.lib.oracle_observe_batch_p(ctypes.byref(params.as_c()), envs.ctypes.data, len(envs),
+                                            _ptr(obs, ctypes.c_double))
         return obs
 
-    def reset(self, envs: np.ndarray) -> np.ndarray:
+    def reset(self, envs: np.ndarray, params: OracleParams | None = None) -> np.ndarray:
         obs = np.empty((len(envs), 10), np.float64)
-        self.lib.oracle_reset_batch(envs.ctypes.data, len(envs), _ptr(obs, ctypes.c_double))
+        if params is None:
+            self.lib.oracle_reset_batch(envs.ctypes.data, len(envs), _ptr(obs, ctypes.c_double))
+        else:
+            self.lib.oracle_reset_batch_p(ctypes.byref(params.as_c()), envs.ctypes.data, len(envs),
+                                          _ptr(obs, ctypes.c_double))
         return obs
 
-    def step(self, envs, a1, a2=None, autoreset=False, final_obs=False, stats=None):
+    def collided(self, envs: np.ndarray, params: OracleParams | None = None) -> np.ndarray:
+        """is_collided() (merging_env.py:198-206) of every env, no state change."""
+        coll = np.empty(len(envs), np.uint8)
+        self.lib.oracle_collided_batch_p(ctypes.byref((params or DEFAULT_PARAMS).as_c()), envs.ctypes.data,
+                                         len(envs), _ptr(coll, ctypes.c_uint8))
+        return coll
+
+    def step(self, envs, a1, a2=None, autoreset=False, final_obs=False, stats=None, params=None):
         """One step of every env. Returns obs[n,10] f64, rew[n,2] f64, done[n] u8, coll[n] u8,
         status[n] u32 (MG_ST_* bits), and final_obs[n,10] (NaN rows for envs not finished).
         stats = (ret_sum [n,3] f64, counts [n,6] u32), accumulated at autoreset: the sums of
@@ -366,17 +473,24 @@ class COracle:
         status = np.empty(n, np.uint32)
         fobs = np.full((n, 10), np.nan) if final_obs else None
         ret_sum, counts = (None, None) if stats is None else stats
-        err = self.lib.oracle_step_batch(
-            envs.ctypes.data, n, _ptr(a1, ctypes.c_int8), _ptr(a2, ctypes.c_int8),
-            int(bool(autoreset)), _ptr(obs, ctypes.c_double), _ptr(rew, ctypes.c_double),
-            _ptr(done, ctypes.c_uint8), _ptr(coll, ctypes.c_uint8), _ptr(fobs, ctypes.c_double),
-            _ptr(ret_sum, ctypes.c_double), _ptr(counts, ctypes.c_uint32),
-            _ptr(status, ctypes.c_uint32), 0)
+        args = (envs.ctypes.data, n, _ptr(a1, ctypes.c_int8), _ptr(a2, ctypes.c_int8),
+                int(bool(autoreset)), _ptr(obs, ctypes.c_double), _ptr(rew, ctypes.c_double),
+                _ptr(done, ctypes.c_uint8), _ptr(coll, ctypes.c_uint8), _ptr(fobs, ctypes.c_double),
+                _ptr(ret_sum, ctypes.c_double), _ptr(counts, ctypes.c_uint32),
+                _ptr(status, ctypes.c_uint32))
+        if params is None:
+            err = self.lib.oracle_step_batch(*args, 0)
+        else:
+            err = self.lib.oracle_step_batch_p(ctypes.byref(params.as_c()), *args)
         return obs, rew, done, coll, status, fobs, err
 
     def mpc_first_accel(self, x0, v0, xt, vt, t=3.0):
         """mpc_1d(x0, v0, xt, vt, t).action() with the QP solved in C (helper.py:152-191)."""
         return float(self.lib.oracle_mpc_first_accel(x0, v0, xt, vt, t))
+
+    def mpc_first_accel_p(self, params: OracleParams, x0, v0, action):
+        """action_to_acc (merging_env.py:134-136, :147) of `action` from (x0, v0) under params."""
+        return float(self.lib.oracle_mpc_first_accel_p(ctypes.byref(params.as_c()), x0, v0, int(action)))
 
     def philox(self, ctr, key):
         c = np.ascontiguousarray(ctr, np.uint32)
@@ -400,14 +514,16 @@ class COracle:
         return a1, a2
 
     def rollout_random(self, envs, steps, seed, first_step, opponent_random, env_offset=0,
-                       stats=None):
+                       stats=None, params=None):
         """`steps` autoreset steps with Philox actions (the bench workload). Returns the
         number of env-steps done."""
         ret_sum, counts = (None, None) if stats is None else stats
-        return int(self.lib.oracle_rollout_random(
-            envs.ctypes.data, len(envs), int(steps), int(seed), int(first_step),
-            int(opponent_random), int(env_offset), _ptr(ret_sum, ctypes.c_double),
-            _ptr(counts, ctypes.c_uint32)))
+        args = (envs.ctypes.data, len(envs), int(steps), int(seed), int(first_step),
+                int(opponent_random), int(env_offset), _ptr(ret_sum, ctypes.c_double),
+                _ptr(counts, ctypes.c_uint32))
+        if params is None:
+            return int(self.lib.oracle_rollout_random(*args))
+        return int(self.lib.oracle_rollout_random_p(ctypes.byref(params.as_c()), *args))
 
 
 # --------------------------------------------------------------------------- DQN policy oracle
@@ -656,7 +772,7 @@ def stats_reduce_fixed(records):
     return sums, [int(c) for c in cnt]
 
 
-def oracle_envs_from(coracle, state, idx=None):
+def oracle_envs_from(coracle, state, idx=None, params=None):
     """C-oracle envs holding a device batch's state (MergeVecEnv or its state_dict), for replaying
     it from mid-episode: positions, speeds, returns, step count, winner, the float clock the
     count stands for, and main.py's running ep_reward (r1_accumulate, or the ego's
@@ -673,7 +789,8 @@ def oracle_envs_from(coracle, state, idx=None):
     envs["steps"] = tf & 0x1FFF
     envs["winner"] = (tf & 0x6000) >> 13
     envs["done"] = (tf & 0x8000) != 0
-    envs["time_stamp"] = np.cumsum(np.full(8200, 0.2))[np.maximum(envs["steps"] - 1, 0)] * (envs["steps"] > 0)
+    envs["time_stamp"] = np.cumsum(np.full(8200, float((params or DEFAULT_PARAMS).dT)))[
+        np.maximum(envs["steps"] - 1, 0)] * (envs["steps"] > 0)
     pending = None
     if isinstance(state, dict) and "episode_stats" in state:
         pending = sel(state["episode_stats"])[:, 3].cpu().numpy()
@@ -684,18 +801,18 @@ def oracle_envs_from(coracle, state, idx=None):
     return envs
 
 
-def step_with_won(coracle, envs, a1, a2=None):
+def step_with_won(coracle, envs, a1, a2=None, params=None):
     """One autoreset step of the C oracle that also reports env.winner == 1 after the step,
     read before the reset (the kernels' won bit; main.py:209). Returns obs (reset observation
     where done), rew, done, coll, final_obs (NaN rows where not done), won, err."""
-    obs, rew, done, coll, _, _, err = coracle.step(envs, a1, a2, autoreset=False)
+    obs, rew, done, coll, _, _, err = coracle.step(envs, a1, a2, autoreset=False, params=params)
     won = envs["winner"] == 1
     d = done.astype(bool)
     fobs = np.full_like(obs, np.nan)
     fobs[d] = obs[d]
     if d.any():
         sub = envs[d]
-        obs[d] = coracle.reset(sub)
+        obs[d] = coracle.reset(sub, params)
         envs[d] = sub
     return obs, rew, done, coll, fobs, won, err
 

@@ -171,12 +171,26 @@ def test_fused_hdqn_rollout(coracle, n, opponent):
     between, its action the lower net's on [goal_op] + swapped state (:299-300). opponent
     "other" (any other Strategy_OP, :265-268): the same, with a second pair of nets standing in
     for the checkpoint load_path_op holds (the kernel reads them from global memory)."""
+    _fused_hdqn_rollout(coracle, n, opponent)
+
+
+def test_fused_hdqn_rollout_at_params(coracle):
+    """The same checks at case A of tests/params_cases.py (every mg_params field off its default):
+    577 envs, two launches of 16 steps from scattered mid-episode states, against the parametrised
+    oracle -- transitions, goal_status on the fp64 state, the reset goal (the meta-net's argmax on
+    THIS case's reset observation), rings, statistics and q_eval."""
+    _fused_hdqn_rollout(coracle, 577, "none", case="A", T=16)
+
+
+def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
     import torch
 
+    import params_cases as pc
     from merging_gym import MergeVecEnv, ReplayRing
     from merging_gym.policy import NUM_GOALS, QNet, greedy_threshold
 
-    T, seed, dev = 24, 9, "cuda:0"
+    seed, dev = 9, "cuda:0"
+    params = None if case is None else pc.CASES[case]
     rng = np.random.default_rng(21)
     mk = _net_signed if opponent.endswith("-signed") else _net
     meta_sd, lower_sd = mk(rng, 10, NUM_GOALS), mk(rng, 11, 5)
@@ -192,20 +206,25 @@ def test_fused_hdqn_rollout(coracle, n, opponent):
     thr = greedy_threshold()
     env = MergeVecEnv(n, device=dev, final_observation=True)
     k0 = 190
-    for k in range(k0):
-        env.step_random(5, opponent_random=False, step_idx=k)
-    envs = mo.oracle_envs_from(coracle, env)
+    if case is None:
+        for k in range(k0):
+            env.step_random(5, opponent_random=False, step_idx=k)
+    else:
+        pc.fill_native(env.params, case)
+        env.reset()
+        pc.load_scattered_device(env, case, np.random.default_rng(n))
+    envs = mo.oracle_envs_from(coracle, env, params=params)
     stats = (env.returns.cpu().numpy().copy(), env.counts.cpu().numpy().astype(np.uint32))
     qe, qe_abs = env.q_eval.cpu().numpy().copy(), np.zeros(n)  # hdqn.py:330's q_eval per episode
     qe_pin = qe.copy()  # the same sums of the kernel-order Q-values (choice_check.order_matched_q)
     obs = env.observe().cpu().numpy().copy()
-    obs64 = coracle.observe(envs)  # the fp64 state goal_status reads
+    obs64 = coracle.observe(envs, params)  # the fp64 state goal_status reads
     kind = _kind(opponent)
     cc_a = ChoiceCheck(f"fused h-DQN {opponent} n={n}: ego actions", max_frac=MAX_EXCUSED[kind])
     cc_g = ChoiceCheck(f"fused h-DQN {opponent} n={n}: goals", max_frac=MAX_EXCUSED["signed" if kind == "signed" else "uniform"])
     cc_o = ChoiceCheck(f"fused h-DQN {opponent} n={n}: opponent", max_frac=MAX_EXCUSED[kind])
-    reset_goal = meta.reset_argmax()
-    reset_obs = coracle.reset(coracle.new_envs(1)).astype(np.float32)
+    reset_goal = meta.reset_argmax(None if case is None else env.params)
+    reset_obs = coracle.reset(coracle.new_envs(1), params).astype(np.float32)
     q_reset = mo.qnet_reference(meta_sd, reset_obs, bf16=True)
     ChoiceCheck("reset goal").check([reset_goal], q_reset.argmax(1), [True], q_reset, q_exact=exact_q(meta_sd, reset_obs))
     fresh_off = -(1 << 63)  # counter (env ^ 2^63, step): the fresh-goal stream
@@ -276,7 +295,8 @@ def test_fused_hdqn_rollout(coracle, n, opponent):
                            q_exact=exact_q(op_lower_sd, xo))
                 a2 = a2_all[t].astype(np.int8)
             o_obs, o_rew, o_done, o_coll, _, o_fobs, err = coracle.step(envs, a1_all[t].astype(np.int8), a2,
-                                                                        autoreset=True, final_obs=True, stats=stats)
+                                                                        autoreset=True, final_obs=True, stats=stats,
+                                                                        params=params)
             assert err == 0
             np.testing.assert_array_equal(done_all[t], o_done.astype(bool), err_msg=str(t))
             np.testing.assert_allclose(o_all[t], o_obs.astype(np.float32), **OBS_TOL)
@@ -353,6 +373,10 @@ def test_fused_hdqn_rollout(coracle, n, opponent):
                             reward=rows["r_int"][t][None])
     assert ring_f.memory_counter == c
     np.testing.assert_array_equal(ring_f.memory.cpu().numpy(), mem_f)
+    if case is not None:  # fp64 state bit for bit
+        for name, src in (("pos1", env.p1), ("vel1", env.v1), ("pos2", env.p2), ("vel2", env.v2),
+                          ("r1_acc", env.ret1), ("r2_acc", env.ret2)):
+            np.testing.assert_array_equal(src.cpu().numpy(), envs[name], err_msg=name)
     assert ring_m.memory_counter == c_m > 200  # Goal_DQN's ring wrapped
     np.testing.assert_array_equal(ring_m.memory.cpu().numpy(), mem_m)
     np.testing.assert_array_equal(env.hdqn_ext.cpu().numpy(), acc)

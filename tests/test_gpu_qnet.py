@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import merge_oracle as mo
+import params_cases as pc
 from choice_check import ChoiceCheck, check_q_eval, exact_q, order_matched_q
 from conftest import ROOT
 
@@ -154,14 +155,35 @@ def test_rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, 
     may-finish ones at once -- the round-5 lists' extremes: an ego wave whose every item writes its
     Q-values into the tile rows, and opponent lists whose may-finish items reach the tail that the
     env waves run (they then publish the rows-read flag the ego waves wait for)."""
+    _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync)
+
+
+@pytest.mark.parametrize("opponent", ["none", "self"])
+@pytest.mark.parametrize("case", ["A", "D"])
+def test_rollout_qnet_policy_and_transitions_at_params(torch, coracle, nets, case, opponent):
+    """The same checks away from the default mg_params (tests/params_cases.py): 577 envs x 32 steps
+    from scattered mid-episode states, some a few steps from timeout_steps. Every transition equals
+    the parametrised C oracle's, and the logged q_eval -- which needs may_finish_next, with
+    finish_bound's constants for these params, to flag every finishing step -- is checked against the
+    bf16 reference, the kernel-order forward and the oracle's MFMA model of it."""
+    _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, 577, False, case=case, T=32)
+
+
+def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync, case=None, T=24):
     from merging_gym import MergeVecEnv
     from merging_gym.policy import QNet, greedy_threshold
 
-    T, seed, k0 = 24, 17, 500 + n % 2  # odd sizes start on an odd step (the second word pair of a call)
+    seed, k0 = 17, 500 + n % 2  # odd sizes start on an odd step (the second word pair of a call)
+    params = None if case is None else pc.CASES[case]
     qnet = QNet.from_state_dict(nets["l1"], device="cuda:0")
     env = MergeVecEnv(n, device="cuda:0")
-    for k in range(200):  # mid-episode start: episodes end inside the window (autoreset, q_eval)
-        env.step_random(seed + 1, step_idx=k)
+    if case is None:
+        for k in range(200):  # mid-episode start: episodes end inside the window (autoreset, q_eval)
+            env.step_random(seed + 1, step_idx=k)
+    else:
+        pc.fill_native(env.params, case)
+        env.reset()
+        pc.load_scattered_device(env, case, np.random.default_rng(n))
     if sync:  # the clock's bits of the packed time / flags word (MG_TF_*)
         m = env._nat.TF_STEPS_MASK
         env.tf.copy_((env.tf & ~m) | 2498)
@@ -172,7 +194,7 @@ def test_rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, 
         envs[name] = src.cpu().numpy()
     envs["steps"] = env.steps.cpu().numpy()
     envs["winner"] = env.winner.cpu().numpy()
-    envs["time_stamp"] = np.cumsum(np.full(2700, 0.2))[np.maximum(envs["steps"] - 1, 0)] * (envs["steps"] > 0)
+    envs["time_stamp"] = (params or mo.DEFAULT_PARAMS).clock(envs["steps"])
     obs_in = env.observe().cpu().numpy().copy()
     opp_key = "l3" if opponent == "other" else "l1"
     opp = QNet.from_state_dict(nets["l3"], device="cuda:0") if opponent == "other" else opponent
@@ -204,7 +226,7 @@ def test_rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, 
                       q_exact=exact_q(nets[opp_key], obs_in, swap=True))
         # the transition, with the actions the kernel took
         o_obs, o_rew, o_done, o_coll, _, o_fobs, err = coracle.step(
-            envs, traj["a1"][t], traj["a2"][t], autoreset=True, final_obs=True)
+            envs, traj["a1"][t], traj["a2"][t], autoreset=True, final_obs=True, params=params)
         assert err == 0
         np.testing.assert_array_equal(traj["done"][t], o_done.astype(bool), err_msg=str(t))
         np.testing.assert_array_equal(traj["collision"][t], o_coll.astype(bool), err_msg=str(t))
@@ -224,8 +246,14 @@ def test_rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, 
         obs_in = traj["obs"][t]
     np.testing.assert_array_equal(env.p1.cpu().numpy(), envs["pos1"])
     np.testing.assert_array_equal(env.ret2.cpu().numpy(), envs["r2_acc"])
-    check_q_eval(env.q_eval.cpu().numpy(), qe, qe_abs, f"rollout ego l1 ({opponent}, n={n})", pinned=qe_pin,
-                 model=qe_model)
+    if case is not None:
+        for name, src in (("pos2", env.p2), ("vel1", env.v1), ("vel2", env.v2), ("r1_acc", env.ret1)):
+            np.testing.assert_array_equal(src.cpu().numpy(), envs[name], err_msg=name)
+        np.testing.assert_array_equal(env.steps.cpu().numpy(), envs["steps"])
+        np.testing.assert_array_equal(env.winner.cpu().numpy(), envs["winner"])
+        assert traj["done"].sum() > 50 and traj["collision"].sum() > 0, (traj["done"].sum(), traj["collision"].sum())
+    check_q_eval(env.q_eval.cpu().numpy(), qe, qe_abs, f"rollout ego l1 ({opponent}, n={n}, {case or 'default'})",
+                 pinned=qe_pin, model=qe_model)
     assert env._step_idx == k0 + T
     cc1.finish()
     if opponent in ("self", "other"):
@@ -394,15 +422,36 @@ def test_q_eval_with_non_default_vehicle_boxes(torch, nets, opponent):
     plus the arc's lateral drift), not the default boxes' 5.75 / 9 m: with 14 x 30 m boxes the cars
     collide far earlier, and every episode's logged q_eval must still be eval_net(state)[action] of
     its last step (main.py:221) -- the oracle MFMA rule's Q row of the kernel's own input
-    observation -- on explore steps too. (The env dynamics at these params have no oracle; the
-    transitions are the kernel's.)"""
+    observation -- on explore steps too. The reference here is that rule on the kernel's own inputs
+    and the kernel's own done flags; the env dynamics away from the default params are compared with
+    the parametrised oracle in test_rollout_qnet_policy_and_transitions_at_params and
+    tests/test_gpu_params.py."""
+    _q_eval_on_own_inputs(torch, nets, opponent, 4096, None)
+
+
+@pytest.mark.parametrize("opponent", ["none", "self"])
+def test_q_eval_on_the_tight_arc(torch, nets, opponent):
+    """Case B of tests/params_cases.py (R = 300, speeds to 200: angle0 = 1.28, finish_bound's lateral
+    reach 71 m where four passes gave 68): 1,024 envs. Being the MFMA rule on the kernel's own inputs
+    and done flags, this check is immune to the one-ulp difference between glibc's and the device
+    library's sin / cos at wide angles, which can move a touching-box collision flag; B is for that
+    reason not compared flag for flag with the oracle on the GPU, only on the CPU
+    (tests/test_host_step.py)."""
+    _q_eval_on_own_inputs(torch, nets, opponent, 1024, "B")
+
+
+def _q_eval_on_own_inputs(torch, nets, opponent, n, case):
     from merging_gym import MergeVecEnv
     from merging_gym.policy import QNet
 
-    n, T, seed = 4096, 48, 3
+    T, seed = 48, 3
     env = MergeVecEnv(n, device="cuda:0")
-    env.params.veh_w, env.params.veh_h = 14, 30
-    for k in range(150):
+    if case is None:
+        env.params.veh_w, env.params.veh_h = 14, 30
+    else:
+        pc.fill_native(env.params, case)
+        env.reset()
+    for k in range(150 if case is None else 40):
         env.step_random(seed + 1, step_idx=k)
     env.clear_statistics()
     qnet = QNet.from_state_dict(nets["l1"], device="cuda:0")
@@ -419,7 +468,8 @@ def test_q_eval_with_non_default_vehicle_boxes(torch, nets, opponent):
             q = mo.qnet_reference_mfma(nets["l1"], obs_in, form=form).astype(np.float64)
             exp += np.where(d, q[np.arange(n), a1[t].astype(np.int64)], 0.0)
         obs_in = obs[t]
-    assert coll.sum() > 100 and done.sum() > 500, (int(coll.sum()), int(done.sum()))
+    print(f"[q_eval own inputs {case or 'boxes'} {opponent}] {int(coll.sum())} collisions, {int(done.sum())} finishes")
+    assert coll.sum() > (100 if case is None else 10) and done.sum() > 500, (int(coll.sum()), int(done.sum()))
     got = env.q_eval.cpu().numpy()
     bad = np.flatnonzero(got != exp)
     assert bad.size == 0, (bad.size, bad[:8].tolist(), got[bad[:4]].tolist(), exp[bad[:4]].tolist())

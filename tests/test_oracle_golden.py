@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import merge_oracle as mo
+import params_cases as pc
 
 TRACES = [f"kat{k}" for k in "ABCDEFG"] + ["rndL0", "rndRR", "past"]
 FTOL = 1e-9
@@ -31,13 +32,14 @@ def _winner(w):
     return 0 if w is None else w
 
 
-@pytest.mark.parametrize("trace", TRACES)
-def test_python_oracle_replays_reference_trace(golden, trace):
-    env = mo.PyMergeEnv()
+def _replay_py(golden, trace, params=None):
+    env = mo.PyMergeEnv(params)
     g = {k[len(trace) + 1:]: golden[k] for k in golden.files if k.startswith(trace + "_")}
     for k in range(len(g["a1"])):
         if g["reset"][k]:
             obs, rew, done, coll = env.reset(), [0.0, 0.0], False, False
+            if k == 0 and "k0" in g and g["k0"] > 0:  # a timeout trace starts late on the clock
+                env.time_stamp = float(params.clock(int(g["k0"])))
         else:
             a2 = int(g["a2"][k])
             obs, rew, done, info = env.step(int(g["a1"][k]), None if a2 < 0 else a2)
@@ -55,15 +57,22 @@ def test_python_oracle_replays_reference_trace(golden, trace):
         assert env.time_stamp == g["time"][k]
 
 
-def _replay_c(coracle, golden, trace):
+@pytest.mark.parametrize("trace", TRACES)
+def test_python_oracle_replays_reference_trace(golden, trace):
+    _replay_py(golden, trace)
+
+
+def _replay_c(coracle, golden, trace, params=None):
     g = {k[len(trace) + 1:]: golden[k] for k in golden.files if k.startswith(trace + "_")}
     envs = coracle.new_envs(1)
     for k in range(len(g["a1"])):
         if g["reset"][k]:
-            obs = coracle.reset(envs)[0]
+            obs = coracle.reset(envs, params)[0]
             rew, done, coll = np.zeros(2), 0, 0
+            if k == 0 and "k0" in g and g["k0"] > 0:
+                envs["time_stamp"] = params.clock(int(g["k0"]))
         else:
-            o, r, d, c, st, _, err = coracle.step(envs, g["a1"][k:k + 1], g["a2"][k:k + 1])
+            o, r, d, c, st, _, err = coracle.step(envs, g["a1"][k:k + 1], g["a2"][k:k + 1], params=params)
             assert err == 0
             obs, rew, done, coll = o[0], r[0], d[0], c[0]
             # the status bits that mark Python ints (rewards 0 / -10, vel int 0)
@@ -88,6 +97,54 @@ def _replay_c(coracle, golden, trace):
 @pytest.mark.parametrize("trace", TRACES)
 def test_c_oracle_replays_reference_trace(coracle, golden, trace):
     _replay_c(coracle, golden, trace)
+
+
+# ---- the parametrised oracle against the reference run at non-default constants ------------------
+# tests/golden/reference_params_golden.npz (gen_params_golden.py): cases A-D of tests/params_cases.py,
+# the reference's module globals and action_dict set to the case. Same bars as above. Case E (the
+# reference's three literals) cannot be run by the reference and is not in the file.
+PARAM_TRACES = ["same", "ego", "opp", "slow", "toL0", "toOpp", "rndL0", "rndRR"]
+
+
+@pytest.fixture(scope="module")
+def params_golden():
+    import os
+
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                "reference_params_golden.npz"))
+
+
+@pytest.mark.parametrize("trace", PARAM_TRACES)
+@pytest.mark.parametrize("case", pc.REFERENCE_CASES)
+def test_python_oracle_replays_reference_trace_at_params(params_golden, case, trace):
+    _replay_py(params_golden, f"{case}_{trace}", pc.CASES[case])
+
+
+@pytest.mark.parametrize("trace", PARAM_TRACES)
+@pytest.mark.parametrize("case", pc.REFERENCE_CASES)
+def test_c_oracle_replays_reference_trace_at_params(coracle, params_golden, case, trace):
+    _replay_c(coracle, params_golden, f"{case}_{trace}", pc.CASES[case])
+
+
+def test_params_golden_covers_every_ending(params_golden):
+    """Each case's traces hold a collision, an episode ended by each car arriving second and a
+    timeout (the time limit stays the reference's 500 s in A-D)."""
+    for case in pc.REFERENCE_CASES:
+        ends = set()
+        for trace in PARAM_TRACES:
+            g = lambda k: params_golden[f"{case}_{trace}_{k}"]  # noqa: E731
+            for i in np.flatnonzero(g("done")):
+                ends.add("coll" if g("coll")[i] else "timeout" if g("time")[i] > 500 else f"w{g('winner')[i]}")
+        assert ends >= {"coll", "timeout", "w1", "w2"}, (case, ends)
+
+
+def test_timeout_steps_by_accumulation():
+    """timeout_steps is the first k at which k sequential fp64 additions of dT exceed the limit: 0.1
+    overshoots 500 one step early."""
+    assert [pc.timeout_steps(d) for d in (0.1, 0.25, 0.5, 0.2)] == [5000, 2001, 1001, 2501]
+    assert pc.CASES["E"].timeout_steps() == pc.timeout_steps(0.2, 60)
+    for case in pc.CASES.values():
+        assert case.timeout_steps() == pc.timeout_steps(case.dT, case.time_limit) <= 8191
 
 
 def test_known_answers(golden):
