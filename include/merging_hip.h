@@ -36,6 +36,10 @@
  *                     HOST memory, for the single env of BASELINE config 1 (the reference's CPU
  *                     MergeEnv, merging_env.py:118-230, driven one step at a time by
  *                     scripts/human_player.py:112-187 and the scripts' list API)
+ *   mg_dqn_learn / mg_dqn_learner_init / mg_dqn_learner_bytes / mg_dqn_learn_scratch_bytes /
+ *   mg_host_dqn_learn (ABI 21): DQN.learn (scripts/main.py:122-157; HDQN.learn hdqn.py:186-221,
+ *                     Goal_DQN.learn hdqn.py:104-139) -- the minibatch update from the replay ring:
+ *                     Double-DQN target, MSE, Adam, the target copy; fp32 in a documented order
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -60,7 +64,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 20
+#define MG_ABI_VERSION 21
 #define MG_OBS_DIM 10   /* merging_env.py:75 observation_shape = (10) */
 #define MG_NUM_ACTIONS 5 /* merging_env.py:101-102 action_dict / Discrete(5) */
 #define MG_ACTION_NONE (-1) /* action2=None: the constant-speed "L0" opponent, merging_env.py:152 */
@@ -520,6 +524,84 @@ int mg_host_step(const mg_params* params, const mg_state* state, const int8_t* a
 int mg_host_reset(const mg_params* params, const mg_state* state, const uint8_t* mask,
                   const mg_outputs* out, int64_t n);
 int mg_host_observe(const mg_params* params, const mg_state* state, const mg_outputs* out, int64_t n);
+
+/* ---- DQN.learn on the device, ABI 21 --------------------------------------------------------------
+ * One learner serves DQN.learn (scripts/main.py:122-157, Net 10 -> 5), HDQN.learn (hdqn.py:186-221,
+ * 11 -> 5 on the 24-float goal rows) and Goal_DQN.learn (hdqn.py:104-139, 10 -> 3): Double-DQN target,
+ * MSE loss, Adam (main.py:96, lr 0.01), the target net copied from the eval net every target_period
+ * learns (main.py:125-127). Net is main.py:30-47: Linear(in, 200), ReLU, Linear(200, 100), ReLU,
+ * Linear(100, out).
+ *
+ * The learner is one caller-owned device buffer of mg_dqn_learner_bytes(in_dim, out_dim) = 16 P bytes,
+ * P = 200 in + 200 + 20000 + 100 + 100 out + out: four blocks of P contiguous fp32 -- eval parameters,
+ * target parameters, Adam's exp_avg (m), Adam's exp_avg_sq (v) -- each in torch's parameter order
+ * fc1.weight [200, in], fc1.bias, fc2.weight [100, 200], fc2.bias, out.weight [out, 100], out.bias.
+ * mg_dqn_learner_init copies six fp32 device tensors into eval and target and zeroes m and v.
+ *
+ * A row of the replay memory is [x(in), a, r, x'(in)], row_floats = 2 in + 2 (mg_replay_store's 22-
+ * and 24-float rows). The minibatch of update u is exactly what mg_replay_sample(seed, draw =
+ * first_draw + u, filled_only) returns for the same ring.
+ *
+ * Arithmetic: fp32, in this fixed order -- the same for every grid, with no float atomics -- where
+ * fmaf is the correctly rounded fused multiply-add and every other operation is rounded once:
+ *   forward, per layer  y[b, j] = fmaf(x[b, K-1], W[j, K-1], ... fmaf(x[b, 0], W[j, 0], bias[j])), k
+ *                       ascending; the hidden layers keep h = y > 0 ? y : 0. Three passes: eval on x,
+ *                       eval on x', target on x'.
+ *   target and loss     a = the row's action column truncated to int (kept inside 0 .. out - 1; NaN: 0);
+ *                       am = argmax_j eval(x')[j], lowest index on ties; t = r + gamma * target(x')[am]
+ *                       (one product, one add); d[b] = eval(x)[a] - t;
+ *                       loss = (((0 + d[0] d[0]) + d[1] d[1]) + ...) * fp32(1 / B);
+ *                       dq[b, a] = d[b] * fp32(2 / B), 0 for the other actions.
+ *   backward, per layer dW[j, k] = the fmaf chain over b ascending of dy[b, j] x[b, k] from +0;
+ *                       db[j] = ((0 + dy[0, j]) + dy[1, j]) + ...;
+ *                       dx[b, k] = the fmaf chain over j ascending of dy[b, j] W[j, k] from +0, then 0
+ *                       where the layer's input h[b, k] is not > 0.
+ *   Adam, per parameter m = fmaf(fp32(1 - beta1), g, fp32(beta1) * m);
+ *                       v = fmaf(fp32(1 - beta2) * g, g, fp32(beta2) * v);
+ *                       den = sqrtf(v) / fp32(sqrt(1 - beta2^s)) + fp32(eps);
+ *                       p = p - fp32(lr / (1 - beta1^s)) * (m / den), s = update number + 1;
+ *                       the scalars inside fp32( ) are computed on the host in double (libm pow and
+ *                       sqrt) and rounded once.
+ *   target copy         before update number t = first_update + u (counted from 0), when
+ *                       t % target_period == 0, target = eval.
+ * gamma is rounded to fp32 once. fp32 division and sqrtf are correctly rounded on both sides, so
+ * mg_host_dqn_learn -- the same functions on HOST pointers, synchronously, like mg_host_step -- gives
+ * the kernels' bits.
+ *
+ * mg_dqn_learn enqueues num_updates updates back to back on `stream` with no host synchronisation:
+ * seven launches each (layer 1 with the row gather, layer 2, layer 3 with target and dq, three
+ * backward layers, Adam), one more when the target copy is due. loss_out [num_updates] and rows_out
+ * [num_updates, batch, row_floats] (the sampled rows) are optional. packed_out (optional, 16-byte
+ * aligned, mg_qnet_packed_bytes()): the eval net after the last update in mg_qnet_pack's layout, so
+ * the acting kernels read the new weights. scratch: mg_dqn_learn_scratch_bytes(batch, in_dim,
+ * out_dim) bytes, 16-byte aligned, any contents, one per stream. Accepted: 1 <= in_dim <= 13,
+ * 1 <= out_dim <= 8, row_floats == 2 in_dim + 2, 1 <= batch <= 1024, 1 <= capacity <= 2^32,
+ * target_period >= 1, 0 <= beta < 1, num_updates >= 0 (0 is a no-op); counter is read only with
+ * filled_only. learner 16-byte, rows and counter 8-byte, loss_out and rows_out 4-byte aligned. */
+typedef struct mg_dqn_hyper {
+  double lr;             /* main.py:13 LR = 0.01 */
+  double gamma;          /* main.py:14 GAMMA = 0.9 */
+  double beta1;          /* torch.optim.Adam's defaults: 0.9, 0.999, 1e-8 */
+  double beta2;
+  double eps;
+  int32_t target_period; /* main.py:17 Q_NETWORK_ITERATION = 100 */
+  int32_t reserved;      /* 0 */
+} mg_dqn_hyper;
+
+size_t mg_dqn_learner_bytes(int32_t in_dim, int32_t out_dim);
+int mg_dqn_learner_init(float* learner, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                        const float* fc2_b, const float* out_w, const float* out_b, int32_t in_dim,
+                        int32_t out_dim, void* stream);
+size_t mg_dqn_learn_scratch_bytes(int32_t batch, int32_t in_dim, int32_t out_dim);
+int mg_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t row_floats,
+                 int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates, uint64_t first_update,
+                 uint64_t seed, uint64_t first_draw, int32_t filled_only, const mg_dqn_hyper* hyper, float* loss_out,
+                 float* rows_out, void* packed_out, void* scratch, size_t scratch_bytes, void* stream);
+int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
+                      int32_t row_floats, int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates,
+                      uint64_t first_update, uint64_t seed, uint64_t first_draw, int32_t filled_only,
+                      const mg_dqn_hyper* hyper, float* loss_out, float* rows_out, void* scratch,
+                      size_t scratch_bytes);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@
 #include "mg_mpc_qp.h"          // mpc_qp_constants (host only)
 #include "mg_stats_reduce.h"    // the fixed-order statistics reduction, goal_status_kernel
 #include "mg_host_env.h"        // the CPU single-env path
+#include "mg_learn.h"           // DQN.learn: the minibatch update kernels and their host twin
 
 extern "C" {
 
@@ -455,6 +456,117 @@ int mg_host_reset(const mg_params* params, const mg_state* state, const uint8_t*
 int mg_host_observe(const mg_params* params, const mg_state* state, const mg_outputs* out, int64_t n) {
   if (int e = check_common(params, state, out, n)) return e;
   for (int64_t i = 0; i < n; ++i) host_observe_env(*params, *state, *out, i);
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- DQN.learn (scripts/main.py:122-157, hdqn.py:104-139, :186-221) -------------------------------
+size_t mg_dqn_learner_bytes(int32_t in_dim, int32_t out_dim) {
+  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut) return 0;
+  return static_cast<size_t>(learn_layout(in_dim, out_dim).total) * 4 * sizeof(float);
+}
+
+int mg_dqn_learner_init(float* learner, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                        const float* fc2_b, const float* out_w, const float* out_b, int32_t in_dim,
+                        int32_t out_dim, void* stream) {
+  if (!learner || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !out_w || !out_b)
+    return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: NULL pointer");
+  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut)
+    return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: need 1 <= in_dim <= 13, 1 <= out_dim <= 8");
+  if (misaligned(learner, 15) || misaligned(fc1_w, 3) || misaligned(fc1_b, 3) || misaligned(fc2_w, 3) ||
+      misaligned(fc2_b, 3) || misaligned(out_w, 3) || misaligned(out_b, 3))
+    return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: learner must be 16-byte, the tensors 4-byte aligned");
+  const LearnLayout O = learn_layout(in_dim, out_dim);
+  const float* src[6] = {fc1_w, fc1_b, fc2_w, fc2_b, out_w, out_b};
+  const int off[7] = {O.w1, O.b1, O.w2, O.b2, O.w3, O.b3, O.total};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  for (int blk = 0; blk < 2; ++blk)  // eval, target
+    for (int k = 0; k < 6; ++k) {
+      const int n = off[k + 1] - off[k];
+      hipLaunchKernelGGL(learn_copy_kernel, dim3(grid_blocks(n)), dim3(kBlock), 0, st, src[k],
+                         learner + blk * O.total + off[k], n);
+    }
+  if (hipError_t e = hipMemsetAsync(learner + 2 * O.total, 0, 2 * sizeof(float) * O.total, st)) {  // m, v
+    std::snprintf(g_err, sizeof(g_err), "mg_dqn_learner_init: %s", hipGetErrorString(e));
+    return static_cast<int>(e);
+  }
+  return finish_launch("mg_dqn_learner_init");
+}
+
+size_t mg_dqn_learn_scratch_bytes(int32_t batch, int32_t in_dim, int32_t out_dim) {
+  if (batch < 1 || batch > 1024 || in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut) return 0;
+  return static_cast<size_t>(learn_scratch(batch, in_dim, out_dim).total) * sizeof(float);
+}
+
+int mg_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t row_floats,
+                 int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates, uint64_t first_update,
+                 uint64_t seed, uint64_t first_draw, int32_t filled_only, const mg_dqn_hyper* hyper, float* loss_out,
+                 float* rows_out, void* packed_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int e = check_learn("mg_dqn_learn", learner, rows, counter, capacity, row_floats, in_dim, out_dim, batch,
+                          num_updates, filled_only, hyper, loss_out, rows_out, packed_out, scratch, scratch_bytes))
+    return e;
+  if (num_updates == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
+  const LearnLayout O = learn_layout(in_dim, out_dim);
+  const int P = O.total;
+  for (int32_t u = 0; u < num_updates; ++u) {
+    const uint64_t t = first_update + static_cast<uint64_t>(u);
+    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), loss_out ? loss_out + u : nullptr,
+                     rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
+    if (t % static_cast<uint64_t>(hyper->target_period) == 0)
+      hipLaunchKernelGGL(learn_copy_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L.eval, L.target, P);
+    hipLaunchKernelGGL(learn_l1_kernel, dim3(grid_blocks(int64_t{3} * batch * kLH1)), dim3(kBlock), 0, st, L);
+    hipLaunchKernelGGL(learn_l2_kernel, dim3((kLH2 + kLTileJ - 1) / kLTileJ, (batch + kLTileB - 1) / kLTileB, 3),
+                       dim3(kLTileJ * kLTileB), 0, st, L);
+    hipLaunchKernelGGL(learn_l3_kernel, dim3((batch + kLRows3 - 1) / kLRows3), dim3(32 * kLRows3), 0, st, L);
+    for (int layer = 3; layer >= 1; --layer) {
+      const LearnBwd G = learn_bwd_layer(L, layer);
+      hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
+    }
+    hipLaunchKernelGGL(learn_adam_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L, P);
+  }
+  if (packed_out)  // the acting kernels' layout of the new eval net, on the same stream
+    return mg_qnet_pack(L.eval + O.w1, L.eval + O.b1, L.eval + O.w2, L.eval + O.b2, L.eval + O.w3, L.eval + O.b3,
+                        in_dim, out_dim, packed_out, stream);
+  return finish_launch("mg_dqn_learn");
+}
+
+int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t row_floats,
+                      int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates, uint64_t first_update,
+                      uint64_t seed, uint64_t first_draw, int32_t filled_only, const mg_dqn_hyper* hyper,
+                      float* loss_out, float* rows_out, void* scratch, size_t scratch_bytes) {
+  if (int e = check_learn("mg_host_dqn_learn", learner, rows, counter, capacity, row_floats, in_dim, out_dim, batch,
+                          num_updates, filled_only, hyper, loss_out, rows_out, nullptr, scratch, scratch_bytes))
+    return e;
+  Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
+  const LearnLayout O = learn_layout(in_dim, out_dim);
+  const int P = O.total;
+  for (int32_t u = 0; u < num_updates; ++u) {
+    const uint64_t t = first_update + static_cast<uint64_t>(u);
+    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), loss_out ? loss_out + u : nullptr,
+                     rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
+    if (t % static_cast<uint64_t>(hyper->target_period) == 0) std::memcpy(L.target, L.eval, sizeof(float) * P);
+    const uint64_t live = learn_rows_live(L.cap, L.counter, L.filled_only);
+    for (int64_t i = 0; i < int64_t{3} * batch * kLH1; ++i) learn_l1_at(L, live, i);
+    for (int pass = 0; pass < 3; ++pass) {  // learn_l2_kernel without its LDS tiles: the same chains
+      const float* Pm = pass == 2 ? L.target : L.eval;
+      for (int64_t b = 0; b < batch; ++b)
+        for (int j = 0; j < kLH2; ++j)
+          L.h2[(pass * int64_t{batch} + b) * kLH2 + j] = learn_relu(
+              learn_fwd(L.h1 + (pass * int64_t{batch} + b) * kLH1, Pm + O.w2 + j * kLH1, Pm[O.b2 + j], kLH1));
+    }
+    for (int b = 0; b < batch; ++b) {
+      float q[3 * kLMaxOut];
+      for (int slot = 0; slot < 3 * out_dim; ++slot) q[slot] = learn_l3_at(L, b, slot);
+      for (int j = 0; j < out_dim; ++j) learn_td_at(L, b, j, q);
+    }
+    for (int layer = 3; layer >= 1; --layer) {
+      const LearnBwd G = learn_bwd_layer(L, layer);
+      for (int64_t i = 0; i < learn_bwd_items(G); ++i) learn_bwd_at(G, i);
+    }
+    for (int i = 0; i < P; ++i) learn_adam_at(L, i);
+  }
   g_err[0] = '\0';
   return 0;
 }

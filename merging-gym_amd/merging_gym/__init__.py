@@ -7,14 +7,18 @@ is importable. Without gym, `merging_gym.make(id)` builds the same envs.
 
 from .envs import MergeEnv, MergeEnvExtend, MergeVecEnv
 
-__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "make", "ENV_IDS"]
+__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "DQNLearner", "make", "ENV_IDS"]
 
 
-def __getattr__(name):  # ReplayRing loads the native library on first use only
+def __getattr__(name):  # ReplayRing and DQNLearner load the native library on first use only
     if name == "ReplayRing":
         from .replay import ReplayRing
 
         return ReplayRing
+    if name == "DQNLearner":
+        from .learn import DQNLearner
+
+        return DQNLearner
     raise AttributeError(name)
 
 ENV_IDS = {

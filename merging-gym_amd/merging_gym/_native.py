@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmerging_hip.so"
 LIB_PATH = os.environ.get("MERGING_HIP_LIB", os.path.join(_HERE, LIB_NAME))
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 OBS_DIM = 10
 NUM_ACTIONS = 5
@@ -65,6 +65,12 @@ class Transitions(_c.Structure):
 
 class HdqnTraj(_c.Structure):
     _fields_ = [(n, _P) for n in ("goal", "next_goal", "reward", "goal_op", "ext_reward", "no_break")]
+
+
+class DqnHyper(_c.Structure):
+    """struct mg_dqn_hyper (ABI 21): DQN.learn's constants (main.py:13-17) and Adam's."""
+    _fields_ = [("lr", _c.c_double), ("gamma", _c.c_double), ("beta1", _c.c_double), ("beta2", _c.c_double),
+                ("eps", _c.c_double), ("target_period", _c.c_int32), ("reserved", _c.c_int32)]
 
 
 class Stats(_c.Structure):
@@ -155,6 +161,18 @@ def _load(path=LIB_PATH):
                                     _c.c_int32, _c.c_int32, _P, _c.c_size_t, _P]
     lib.mg_replay_sample.argtypes = [_P, _P, _c.c_int64, _c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_int32, _P,
                                      _P, _c.c_int64, _P]
+    # ABI 21: DQN.learn on the device and its host twin
+    lib.mg_dqn_learner_bytes.argtypes = [_c.c_int32, _c.c_int32]
+    lib.mg_dqn_learner_bytes.restype = _c.c_size_t
+    lib.mg_dqn_learner_init.argtypes = [_P] * 7 + [_c.c_int32, _c.c_int32, _P]
+    lib.mg_dqn_learn_scratch_bytes.argtypes = [_c.c_int32] * 3
+    lib.mg_dqn_learn_scratch_bytes.restype = _c.c_size_t
+    learn_args = [_P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_uint64,
+                  _c.c_uint64, _c.c_uint64, _c.c_int32, _c.POINTER(DqnHyper), _P, _P]
+    lib.mg_dqn_learn.argtypes = learn_args + [_P, _P, _c.c_size_t, _P]
+    lib.mg_host_dqn_learn.argtypes = learn_args + [_P, _c.c_size_t]
+    for f in (lib.mg_dqn_learner_init, lib.mg_dqn_learn, lib.mg_host_dqn_learn):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

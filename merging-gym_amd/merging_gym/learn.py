@@ -1,0 +1,160 @@
+"""DQNLearner: the reference's learn() on the device.
+
+Device twin of DQN.learn (scripts/main.py:122-157), HDQN.learn (scripts/hdqn.py:186-221) and
+Goal_DQN.learn (hdqn.py:104-139) -- the same code on nets of 10 -> 5, 11 -> 5 and 10 -> 3: a minibatch
+drawn from the replay memory, the Double-DQN target, nn.MSELoss, torch.optim.Adam(lr 0.01) and the
+target net copied from the eval net every Q_NETWORK_ITERATION = 100 learns. One call enqueues any
+number of updates on the current stream (seven kernel launches each, libmerging_hip.so's
+mg_dqn_learn) and repacks the eval net for the acting kernels, so the loop of main.py:189-220 closes
+without leaving the device:
+
+    ring = ReplayRing(2000, device="cuda:0")
+    learner = DQNLearner(QNet.from_state_dict(sd, device="cuda:0"), ring)
+    traj = env.rollout_qnet(16, learner.qnet, seed)       # choose_action + env.step
+    ring.store_rollout(obs0, traj)                         # store_transition
+    learner.learn(4)                                       # learn(), four times
+    traj = env.rollout_qnet(16, learner.qnet, seed, ...)   # acts with the new weights
+
+The arithmetic is fp32 in the fixed order include/merging_hip.h documents, so a run is reproducible
+bit for bit, also across a state_dict() / load_state_dict() resume.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+from . import _native
+from .policy import QNet
+
+KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "out.weight", "out.bias")
+
+
+class DQNLearner:
+    def __init__(self, net, ring, lr: float = 0.01, gamma: float = 0.9, batch_size: int = 128,
+                 target_period: int = 100, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, device=None):
+        """net: a QNet, or a state dict with the reference's keys (fc1.weight ... out.bias); both
+        eval_net and target_net start from it. ring: the ReplayRing learn() draws from; a goal ring
+        (24-float rows) implies in_dim 11. lr, gamma, batch_size, target_period: main.py:13-18's LR,
+        GAMMA, BATCH_SIZE, Q_NETWORK_ITERATION; betas, eps: Adam's. seed: the key of the minibatch
+        draws (update u of the run draws what ring.sample_rows(batch_size, seed, draw=u) returns)."""
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("DQNLearner needs a ROCm GPU; there is no CPU fallback")
+        self._torch = torch
+        self.ring = ring
+        self.device = torch.device(device) if device is not None else ring.device
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self.device != ring.device:
+            raise ValueError(f"the ring lives on {ring.device}, the learner on {self.device}")
+        if isinstance(net, QNet):
+            if net.device != self.device and torch.device(net.device.type, net.device.index or 0) != self.device:
+                raise ValueError(f"the QNet lives on {net.device}, the learner on {self.device}")
+            tensors, qnet = list(net.fp32), net
+        else:
+            tensors = [torch.as_tensor(net[k], dtype=torch.float32).to(self.device).contiguous() for k in KEYS]
+            qnet = None
+        self.in_dim, self.out_dim = int(tensors[0].shape[1]), int(tensors[4].shape[0])
+        if ring.row != 2 * self.in_dim + 2:
+            raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
+                             f"the ring's have {ring.row}")
+        self.batch_size, self.target_period = int(batch_size), int(target_period)
+        self.hyper = _native.DqnHyper(float(lr), float(gamma), float(betas[0]), float(betas[1]), float(eps),
+                                      self.target_period, 0)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.learn_step_counter = 0  # main.py:90, :127 -- a Python int: no device round trip
+        self.draw_counter = 0        # minibatches drawn so far
+
+        nbytes = int(_native.lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
+        if nbytes == 0:
+            raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
+        self._P = nbytes // 16
+        self._buf = torch.empty(4 * self._P, dtype=torch.float32, device=self.device)
+        _native.check(_native.lib.mg_dqn_learner_init(self._buf.data_ptr(), *(t.data_ptr() for t in tensors),
+                                                      self.in_dim, self.out_dim, self._stream()),
+                      "mg_dqn_learner_init")
+        sbytes = int(_native.lib.mg_dqn_learn_scratch_bytes(self.batch_size, self.in_dim, self.out_dim))
+        if sbytes == 0:
+            raise ValueError("batch_size must be in 1..1024")
+        self._scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=self.device)
+        self._scratch_bytes = sbytes
+        # the acting net: its fp32 tensors are views of the eval block, its packed buffer is
+        # rewritten by every learn()
+        self.qnet = qnet if qnet is not None else QNet(*self._views(0), device=self.device)
+        self.qnet.fp32 = self._views(0)
+        self.qnet.__dict__.pop("_reset_argmax", None)
+
+    # ------------------------------------------------------------------ helpers
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _views(self, block):
+        """The six tensors of block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
+        flat = self._buf[block * self._P:(block + 1) * self._P]
+        shapes = ((200, self.in_dim), (200,), (100, 200), (100,), (self.out_dim, 100), (self.out_dim,))
+        out, at = [], 0
+        for s in shapes:
+            n = s[0] * (s[1] if len(s) == 2 else 1)
+            out.append(flat[at:at + n].view(s))
+            at += n
+        return out
+
+    def _repack(self):
+        _native.check(_native.lib.mg_qnet_pack(*(t.data_ptr() for t in self._views(0)), self.in_dim, self.out_dim,
+                                               self.qnet.packed.data_ptr(), self._stream()), "mg_qnet_pack")
+        self.qnet.__dict__.pop("_reset_argmax", None)
+
+    # ------------------------------------------------------------------ learn
+    def learn(self, num_updates: int = 1, filled_only: bool = False, return_loss: bool = False, return_rows: bool = False):
+        """num_updates times learn() (main.py:122-157), enqueued back to back on the current stream;
+        nothing is synchronised. filled_only draws from the rows stored so far instead of the whole
+        memory (the reference learns only once the memory is full, main.py:211). return_loss: the
+        [num_updates] fp32 device tensor of the updates' MSE losses; return_rows: also the
+        [num_updates, B, row] minibatches."""
+        torch = self._torch
+        U = int(num_updates)
+        if U < 0:
+            raise ValueError("num_updates must be >= 0")
+        loss = torch.empty(U, dtype=torch.float32, device=self.device) if return_loss else None
+        rows = torch.empty((U, self.batch_size, self.ring.row), dtype=torch.float32,
+                           device=self.device) if return_rows else None
+        if U > 0:
+            rc = _native.lib.mg_dqn_learn(
+                self._buf.data_ptr(), self.ring.memory.data_ptr(), self.ring._counter.data_ptr(), self.ring.capacity,
+                self.ring.row, self.in_dim, self.out_dim, self.batch_size, U, self.learn_step_counter, self.seed,
+                self.draw_counter, 1 if filled_only else 0, ctypes.byref(self.hyper),
+                None if loss is None else loss.data_ptr(), None if rows is None else rows.data_ptr(),
+                self.qnet.packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes, self._stream())
+            _native.check(rc, "mg_dqn_learn")
+            self.learn_step_counter += U
+            self.draw_counter += U
+            self.qnet.__dict__.pop("_reset_argmax", None)
+        if return_loss and return_rows:
+            return loss, rows
+        return loss if return_loss else rows
+
+    # ------------------------------------------------------------------ checkpoints
+    def eval_state_dict(self):
+        """eval_net.state_dict() as main.py:244 saves it (copies, torch-loadable)."""
+        return {k: t.clone() for k, t in zip(KEYS, self._views(0))}
+
+    def target_state_dict(self):
+        """target_net.state_dict() as main.py:245 saves it."""
+        return {k: t.clone() for k, t in zip(KEYS, self._views(1))}
+
+    def state_dict(self):
+        """Both nets, Adam's moments and the counters: a run resumed from it continues bit for bit."""
+        return {"learner": self._buf.clone(), "in_dim": self.in_dim, "out_dim": self.out_dim,
+                "learn_step_counter": self.learn_step_counter, "draw_counter": self.draw_counter,
+                "seed": self.seed}
+
+    def load_state_dict(self, sd):
+        buf = self._torch.as_tensor(sd["learner"])
+        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim) or buf.numel() != self._buf.numel():
+            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
+        self._buf.copy_(buf.to(self._torch.float32).reshape(-1))
+        self.learn_step_counter = int(sd["learn_step_counter"])
+        self.draw_counter = int(sd["draw_counter"])
+        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        self._repack()
