@@ -137,9 +137,7 @@ int mg_rollout_random(const mg_params* params, const mg_state* state, const mg_t
                       const mg_stats* stats, int64_t n, int64_t env_offset, uint64_t seed,
                       uint64_t first_step, int32_t num_steps, int32_t opponent_random,
                       uint32_t flags, void* stream) {
-  mg_outputs none{};
-  if (int e = check_common(params, state, &none, n)) return e;
-  if (!traj) return fail(hipErrorInvalidValue, "%s", "traj is NULL (pass a zeroed mg_traj)");
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
   if (num_steps < 0 || num_steps > 65535)
     return fail(hipErrorInvalidValue, "%s", "need 0 <= num_steps <= 65535 (split longer rollouts)");
   if (int e = check_traj(traj)) return e;
@@ -156,8 +154,7 @@ int mg_qnet_pack(const float* fc1_w, const float* fc1_b, const float* fc2_w, con
                  void* packed, void* stream) {
   if (!fc1_w || !fc1_b || !fc2_w || !fc2_b || !out_w || !out_b || !packed)
     return fail(hipErrorInvalidValue, "%s", "mg_qnet_pack: NULL pointer");
-  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > 8)
-    return fail(hipErrorInvalidValue, "%s", "mg_qnet_pack: need 1 <= in_dim <= 13, 1 <= out_dim <= 8");
+  if (int e = check_net_dims("mg_qnet_pack", in_dim, out_dim)) return e;
   if (misaligned(packed, 15))
     return fail(hipErrorInvalidValue, "%s", "mg_qnet_pack: packed buffer must be 16-byte aligned");
   const int total = kQFrags * 64 * 8;  // one thread per (fragment, lane, element)
@@ -189,8 +186,7 @@ int mg_qnet_forward(const void* packed, const float* x, int32_t in_dim, int32_t 
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (in_dim < 1 || in_dim > kQMaxIn || (swap_halves && in_dim != kObs))
     return fail(hipErrorInvalidValue, "%s", "mg_qnet_forward: need 1 <= in_dim <= 13 (swap_halves: in_dim 10)");
-  if (misaligned(packed, 15))
-    return fail(hipErrorInvalidValue, "%s", "packed net must be 16-byte aligned");
+  if (int e = check_packed_net(packed, "packed net must be 16-byte aligned")) return e;
   if (n == 0) return 0;
   hipLaunchKernelGGL(qnet_forward_kernel, dim3(grid_blocks(n)), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(packed), x, in_dim,
@@ -203,18 +199,15 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
                     uint64_t first_step, int32_t num_steps, const void* net, int32_t out_dim,
                     uint64_t greedy_threshold, int32_t opponent_mode,
                     uint64_t opp_greedy_threshold, const void* opp_net, uint32_t flags, void* stream) {
-  mg_outputs none{};
-  if (int e = check_common(params, state, &none, n)) return e;
-  if (!traj) return fail(hipErrorInvalidValue, "%s", "traj is NULL (pass a zeroed mg_traj)");
-  if (!net || misaligned(net, 15))
-    return fail(hipErrorInvalidValue, "%s", "net must be a 16-byte aligned packed Q-net");
-  if (num_steps < 0 || out_dim < 1 || out_dim > 8)
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (int e = check_packed_net(net, "net must be a 16-byte aligned packed Q-net")) return e;
+  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
     return fail(hipErrorInvalidValue, "%s", "need num_steps >= 0 and 1 <= out_dim <= 8");
   if (opponent_mode < 0 || opponent_mode > 3)
     return fail(hipErrorInvalidValue, "%s",
                 "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (opp_net)");
-  if (opponent_mode == 3 && (!opp_net || misaligned(opp_net, 15)))
-    return fail(hipErrorInvalidValue, "%s", "opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net");
+  if (opponent_mode == 3)
+    if (int e = check_packed_net(opp_net, "opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net")) return e;
   if (int e = check_traj(traj)) return e;
   if (n == 0 || num_steps == 0) return 0;
   QRollout R = make_rollout<QRollout>(params, state, traj, stats, seed, first_step, env_offset, n, num_steps, flags);
@@ -232,8 +225,7 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
       : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true> : qnet_rollout_ws_kernel<1, false>)
       : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true>
                            : qnet_rollout_ws_kernel<3, true>;
-  launch(kernel, grid_blocks(n, opponent_mode == 3 ? qws_envs<3>() : qws_envs<0>()), kQWsThreads,
-         static_cast<hipStream_t>(stream), R);
+  launch(kernel, grid_blocks(n, kQWsEnvs), kQWsThreads, static_cast<hipStream_t>(stream), R);
   return finish_launch("mg_rollout_qnet");
 }
 
@@ -247,9 +239,7 @@ int mg_rollout_hdqn(const mg_params* params, const mg_state* state, const mg_tra
                     uint64_t* ring_counter, int64_t ring_capacity, uint32_t flags, void* stream) {
   if (ring_rows && (!ring_counter || ring_capacity < 1 || misaligned(ring_rows, 15)))
     return fail(hipErrorInvalidValue, "%s", "ring_rows needs ring_counter, capacity >= 1 and 16-byte alignment");
-  mg_outputs none{};
-  if (int e = check_common(params, state, &none, n)) return e;
-  if (!traj) return fail(hipErrorInvalidValue, "%s", "traj is NULL (pass a zeroed mg_traj)");
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
   if (!goal) return fail(hipErrorInvalidValue, "%s", "goal is NULL (an [n] int8 device array)");
   if (!meta_net || !lower_net || misaligned(meta_net, 15) || misaligned(lower_net, 15))
     return fail(hipErrorInvalidValue, "%s", "meta_net / lower_net must be 16-byte aligned packed Q-nets");
@@ -424,18 +414,7 @@ int mg_host_step(const mg_params* params, const mg_state* state, const int8_t* a
   Launch L = make_launch(params, state, out, stats, n, flags);
   L.a1 = a1;
   L.a2 = a2;
-  for (int64_t w = 0; w < n; w += 64) {  // one 64-env group per done / won mask word
-    uint64_t dm = 0, wm = 0;
-    const int64_t end = n - w < 64 ? n : w + 64;
-    for (int64_t i = w; i < end; ++i) {
-      bool d, won;
-      host_step_env(L, i, d, won);
-      dm |= static_cast<uint64_t>(d) << (i - w);
-      wm |= static_cast<uint64_t>(won) << (i - w);
-    }
-    if (L.O.done_mask) L.O.done_mask[w >> 6] = dm;
-    if (L.O.won_mask) L.O.won_mask[w >> 6] = wm;
-  }
+  host_step_all(L);
   g_err[0] = '\0';
   return 0;
 }
@@ -462,7 +441,7 @@ int mg_host_observe(const mg_params* params, const mg_state* state, const mg_out
 
 // ---- DQN.learn (scripts/main.py:122-157, hdqn.py:104-139, :186-221) -------------------------------
 size_t mg_dqn_learner_bytes(int32_t in_dim, int32_t out_dim) {
-  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut) return 0;
+  if (!net_dims_ok(in_dim, out_dim)) return 0;
   return static_cast<size_t>(learn_layout(in_dim, out_dim).total) * 4 * sizeof(float);
 }
 
@@ -471,8 +450,7 @@ int mg_dqn_learner_init(float* learner, const float* fc1_w, const float* fc1_b, 
                         int32_t out_dim, void* stream) {
   if (!learner || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !out_w || !out_b)
     return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: NULL pointer");
-  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut)
-    return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: need 1 <= in_dim <= 13, 1 <= out_dim <= 8");
+  if (int e = check_net_dims("mg_dqn_learner_init", in_dim, out_dim)) return e;
   if (misaligned(learner, 15) || misaligned(fc1_w, 3) || misaligned(fc1_b, 3) || misaligned(fc2_w, 3) ||
       misaligned(fc2_b, 3) || misaligned(out_w, 3) || misaligned(out_b, 3))
     return fail(hipErrorInvalidValue, "%s", "mg_dqn_learner_init: learner must be 16-byte, the tensors 4-byte aligned");
@@ -494,7 +472,7 @@ int mg_dqn_learner_init(float* learner, const float* fc1_w, const float* fc1_b, 
 }
 
 size_t mg_dqn_learn_scratch_bytes(int32_t batch, int32_t in_dim, int32_t out_dim) {
-  if (batch < 1 || batch > 1024 || in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut) return 0;
+  if (batch < 1 || batch > 1024 || !net_dims_ok(in_dim, out_dim)) return 0;
   return static_cast<size_t>(learn_scratch(batch, in_dim, out_dim).total) * sizeof(float);
 }
 
@@ -541,31 +519,11 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
     return e;
   Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
   const LearnLayout O = learn_layout(in_dim, out_dim);
-  const int P = O.total;
   for (int32_t u = 0; u < num_updates; ++u) {
     const uint64_t t = first_update + static_cast<uint64_t>(u);
     learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), loss_out ? loss_out + u : nullptr,
                      rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
-    if (t % static_cast<uint64_t>(hyper->target_period) == 0) std::memcpy(L.target, L.eval, sizeof(float) * P);
-    const uint64_t live = learn_rows_live(L.cap, L.counter, L.filled_only);
-    for (int64_t i = 0; i < int64_t{3} * batch * kLH1; ++i) learn_l1_at(L, live, i);
-    for (int pass = 0; pass < 3; ++pass) {  // learn_l2_kernel without its LDS tiles: the same chains
-      const float* Pm = pass == 2 ? L.target : L.eval;
-      for (int64_t b = 0; b < batch; ++b)
-        for (int j = 0; j < kLH2; ++j)
-          L.h2[(pass * int64_t{batch} + b) * kLH2 + j] = learn_relu(
-              learn_fwd(L.h1 + (pass * int64_t{batch} + b) * kLH1, Pm + O.w2 + j * kLH1, Pm[O.b2 + j], kLH1));
-    }
-    for (int b = 0; b < batch; ++b) {
-      float q[3 * kLMaxOut];
-      for (int slot = 0; slot < 3 * out_dim; ++slot) q[slot] = learn_l3_at(L, b, slot);
-      for (int j = 0; j < out_dim; ++j) learn_td_at(L, b, j, q);
-    }
-    for (int layer = 3; layer >= 1; --layer) {
-      const LearnBwd G = learn_bwd_layer(L, layer);
-      for (int64_t i = 0; i < learn_bwd_items(G); ++i) learn_bwd_at(G, i);
-    }
-    for (int i = 0; i < P; ++i) learn_adam_at(L, i);
+    host_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0);
   }
   g_err[0] = '\0';
   return 0;

@@ -304,6 +304,13 @@ __device__ __forceinline__ uint4 philox_block(uint64_t gi, uint64_t block, uint6
                        k0, k1);
 }
 
+// The four words of counter (gi, k): one env's draws of step (or call) k.
+__device__ __forceinline__ uint4 philox_env_step(uint64_t gi, uint64_t step, uint64_t seed) {
+  return philox4x32_10(make_uint4(static_cast<uint32_t>(gi), static_cast<uint32_t>(gi >> 32),
+                                  static_cast<uint32_t>(step), static_cast<uint32_t>(step >> 32)),
+                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
+}
+
 constexpr int kStepsPerPhilox = 8;  // steps one Philox4x32-10 call feeds: 4 words x 2 draws
 
 __device__ __forceinline__ void actions_from_block(const uint4& u, uint64_t step, int opp_random, int& a1,

@@ -1,4 +1,4 @@
-// mg_host_env.h -- the CPU single-env path: host_step_env, host_reset_env, host_observe_env.
+// mg_host_env.h -- the CPU single-env path: host_step_env, host_step_all, host_reset_env, host_observe_env.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -69,6 +69,22 @@ void host_step_env(const Launch& L, int64_t i, bool& done, bool& won) {
   }
   if (!L.O.rec64 && L.O.obs) {  // the kernel's observation tile: zeros for a bad action's env
     for (int k = 0; k < kObs; ++k) L.O.obs[i * kObs + k] = r.o[k];
+  }
+}
+
+// Every env of a batch, with the kernel's done / won mask words: one per 64-env group.
+void host_step_all(const Launch& L) {
+  for (int64_t w = 0; w < L.n; w += 64) {
+    uint64_t dm = 0, wm = 0;
+    const int64_t end = L.n - w < 64 ? L.n : w + 64;
+    for (int64_t i = w; i < end; ++i) {
+      bool d, won;
+      host_step_env(L, i, d, won);
+      dm |= static_cast<uint64_t>(d) << (i - w);
+      wm |= static_cast<uint64_t>(won) << (i - w);
+    }
+    if (L.O.done_mask) L.O.done_mask[w >> 6] = dm;
+    if (L.O.won_mask) L.O.won_mask[w >> 6] = wm;
   }
 }
 

@@ -4,6 +4,7 @@
 
 #include "mg_common.h"
 #include "mg_env.h"
+#include "mg_qnet.h"
 #include "mg_step.h"
 
 namespace {
@@ -71,6 +72,29 @@ int check_traj(const mg_traj* traj) {
       misaligned(traj->flags, 3))
     return fail(hipErrorInvalidValue, "%s", "traj.obs must be 16-byte, rew/final_obs 8-byte, flags 4-byte aligned");
   return 0;
+}
+
+// What the three rollouts check first: params, n, the state arrays, then traj itself.
+int check_rollout_args(const mg_params* p, const mg_state* s, const mg_traj* traj, int64_t n) {
+  const mg_outputs none{};
+  if (int e = check_common(p, s, &none, n)) return e;
+  return traj ? 0 : fail(hipErrorInvalidValue, "%s", "traj is NULL (pass a zeroed mg_traj)");
+}
+
+// a packed Q-net (mg_qnet_pack, mg_qnet_fragments): present and 16-byte aligned, or `text`
+int check_packed_net(const void* net, const char* text) {
+  return net && !misaligned(net, 15) ? 0 : fail(hipErrorInvalidValue, "%s", text);
+}
+
+// the widths a net can have (the packed layouts and the learner share them)
+bool net_dims_ok(int32_t in_dim, int32_t out_dim) {
+  return in_dim >= 1 && in_dim <= kQMaxIn && out_dim >= 1 && out_dim <= kLMaxOut;
+}
+
+int check_net_dims(const char* what, int32_t in_dim, int32_t out_dim) {
+  if (net_dims_ok(in_dim, out_dim)) return 0;
+  std::snprintf(g_err, sizeof(g_err), "%s: need 1 <= in_dim <= %d, 1 <= out_dim <= %d", what, kQMaxIn, kLMaxOut);
+  return static_cast<int>(hipErrorInvalidValue);
 }
 
 int finish_launch(const char* what) {

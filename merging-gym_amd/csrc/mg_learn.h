@@ -25,7 +25,6 @@ namespace {
 // and learn_copy_kernel before it when the target net is due (main.py:125-127).
 constexpr int kLH1 = 200;  // main.py:34
 constexpr int kLH2 = 100;  // main.py:36
-constexpr int kLMaxOut = 8;
 constexpr int kLTileJ = 32;  // learn_l2_kernel: units per block
 constexpr int kLTileB = 8;   //                  rows per block
 constexpr int kLBatch = 16;  // loads a chain issues together before it consumes them, in order: a
@@ -394,8 +393,7 @@ int check_learn(const char* what, const float* learner, const float* rows, const
                 const void* packed_out, const void* scratch, size_t scratch_bytes) {
   if (!learner || !rows || !hyper || !scratch || (filled_only && !counter))
     return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
-  if (in_dim < 1 || in_dim > kQMaxIn || out_dim < 1 || out_dim > kLMaxOut)
-    return fail(hipErrorInvalidValue, "%s: need 1 <= in_dim <= 13, 1 <= out_dim <= 8", what);
+  if (int e = check_net_dims(what, in_dim, out_dim)) return e;
   if (row_floats != 2 * in_dim + 2)
     return fail(hipErrorInvalidValue, "%s: row_floats must be 2 * in_dim + 2", what);
   if (batch < 1 || batch > 1024) return fail(hipErrorInvalidValue, "%s: need 1 <= batch <= 1024", what);
@@ -450,6 +448,32 @@ void learn_set_update(Learn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw
   L.A.step = static_cast<float>(h->lr / (1.0 - std::pow(h->beta1, step)));
   L.A.bc2s = static_cast<float>(std::sqrt(1.0 - std::pow(h->beta2, step)));
   L.A.eps = static_cast<float>(h->eps);
+}
+
+// One update on the host (mg_host_dqn_learn), after learn_set_update: the kernels' per-item
+// functions in the kernels' order, so the same fp32 chains.
+void host_learn_update(const Learn& L, const LearnLayout& O, bool sync_target) {
+  if (sync_target) std::memcpy(L.target, L.eval, sizeof(float) * O.total);
+  const int64_t batch = L.B;
+  const uint64_t live = learn_rows_live(L.cap, L.counter, L.filled_only);
+  for (int64_t i = 0; i < 3 * batch * kLH1; ++i) learn_l1_at(L, live, i);
+  for (int pass = 0; pass < 3; ++pass) {  // learn_l2_kernel without its LDS tiles: the same chains
+    const float* Pm = pass == 2 ? L.target : L.eval;
+    for (int64_t b = 0; b < batch; ++b)
+      for (int j = 0; j < kLH2; ++j)
+        L.h2[(pass * batch + b) * kLH2 + j] =
+            learn_relu(learn_fwd(L.h1 + (pass * batch + b) * kLH1, Pm + O.w2 + j * kLH1, Pm[O.b2 + j], kLH1));
+  }
+  for (int b = 0; b < L.B; ++b) {
+    float q[3 * kLMaxOut];
+    for (int slot = 0; slot < 3 * L.out; ++slot) q[slot] = learn_l3_at(L, b, slot);
+    for (int j = 0; j < L.out; ++j) learn_td_at(L, b, j, q);
+  }
+  for (int layer = 3; layer >= 1; --layer) {
+    const LearnBwd G = learn_bwd_layer(L, layer);
+    for (int64_t i = 0; i < learn_bwd_items(G); ++i) learn_bwd_at(G, i);
+  }
+  for (int i = 0; i < O.total; ++i) learn_adam_at(L, i);
 }
 
 }  // namespace

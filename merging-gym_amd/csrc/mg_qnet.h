@@ -50,6 +50,7 @@ constexpr int kQBiasIn = 13;       // first of the three layer-1 input slots hol
 constexpr int kQOne1 = 200;        // hidden-1 units 200..202 = 1.0
 constexpr int kQOne2 = 100;        // hidden-2 units 100..102 = 1.0
 constexpr int kQMaxIn = kQBiasIn;  // widest net input: 13
+constexpr int kLMaxOut = 8;        // widest net output (argmax_first's q[8], the learner's dq rows)
 static_assert(32 * kQT1 >= kQOne1 + 3 && 32 * (kQT1 - 1) < kQH1Real && 16 * kQT2 >= kQOne2 + 3 &&
                   16 * (kQT2 - 1) < kQH2Real && 32 * kQK3 >= 16 * kQT2,
               "tile counts cover the hidden units and their 1.0 units, no tile is all padding");

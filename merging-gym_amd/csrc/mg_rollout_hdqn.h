@@ -81,12 +81,6 @@ __device__ __forceinline__ uint8_t draw_byte(uint32_t explore, uint32_t pick, ui
                                   : (static_cast<uint64_t>(pick) * static_cast<uint64_t>(k)) >> 32);
 }
 
-__device__ __forceinline__ uint4 philox_env_step(uint64_t gi, uint64_t step, uint64_t seed) {
-  return philox4x32_10(make_uint4(static_cast<uint32_t>(gi), static_cast<uint32_t>(gi >> 32),
-                                  static_cast<uint32_t>(step), static_cast<uint32_t>(step >> 32)),
-                       static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-}
-
 // The fresh-goal draws (explore, goal) of step k from stream B (counter gi ^ 2^63). Every opponent
 // but the uniform one uses two words of B per step, so one call serves two steps (ABI 20): call
 // k div 2, words (x, y) on even steps and (z, w) on odd ones; `keep` carries the odd step's pair

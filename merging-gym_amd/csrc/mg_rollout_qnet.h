@@ -18,6 +18,10 @@ constexpr int kQWsEnvWaves = 4;
 constexpr int kQWsIlp = 2;
 constexpr int kQWsThreads = 64 * (4 + kQWsEnvWaves);
 constexpr int kQWsWavesPerSimd = (4 + kQWsEnvWaves) / 4;
+constexpr int kQWsEnvs = 2 * 64 * kQWsEnvWaves * kQWsIlp;  // envs per block
+constexpr int kQWsHalf = kQWsEnvs / 2;                     // envs per group
+constexpr int kQWsTiles = kQWsHalf / 256;                  // 64-env tiles each Q-net wave computes per phase
+static_assert(kQWsTiles >= 1 && kQWsHalf % 256 == 0, "group = 4 Q-net waves x kQWsTiles x 64 envs");
 
 // This lane's rank among the set lanes of a ballot (lanes below it whose bit is set).
 __device__ __forceinline__ int lane_rank(uint64_t m) {
@@ -156,13 +160,14 @@ __device__ __forceinline__ void qnet_put_need(uint8_t* g0, uint8_t* g1, uint8_t 
   }
 }
 
-__device__ __forceinline__ uint4 qnet_draws(const QRollout& R, int64_t i, uint64_t step) {
-  const uint64_t gi = static_cast<uint64_t>(R.env_offset + i);
-  return philox4x32_10(make_uint4(static_cast<uint32_t>(gi), static_cast<uint32_t>(gi >> 32),
-                                  static_cast<uint32_t>(step), static_cast<uint32_t>(step >> 32)),
-                       static_cast<uint32_t>(R.seed), static_cast<uint32_t>(R.seed >> 32));
+// eval_net(state)[0..4] into an env's tile row, once every forward has read its observation: the
+// env wave logs q[action] from it when the episode ends (main.py:221), before it writes the next
+// observation into the row
+__device__ __forceinline__ void put_q_row(float* row, const float (&q)[8]) {
+  reinterpret_cast<f32x2*>(row)[0] = f32x2{q[0], q[1]};
+  reinterpret_cast<f32x2*>(row)[1] = f32x2{q[2], q[3]};
+  row[4] = q[4];
 }
-
 
 // One epsilon-greedy step (main.py:99-112) of the N envs i0 + 64 j of one env-wave lane given their
 // greedy actions, stepped in lockstep. Draws (ABI 20), Philox4x32-10 keyed by seed:
@@ -241,7 +246,7 @@ __device__ __forceinline__ void qnet_policy_step_n(const QRollout& R, Env (&e)[N
     if (t + 1 < R.num_steps) {
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        un[j] = qnet_draws(R, i0 + 64 * j, step + 1);
+        un[j] = philox_env_step(static_cast<uint64_t>(R.env_offset + i0 + 64 * j), step + 1, R.seed);
         qnet_put_need<OPP>(need0 + 64 * j, need1 + 64 * j, qnet_need_bits(R, un[j], live[j], e[j], r[j].o));
       }
     }
@@ -250,17 +255,18 @@ __device__ __forceinline__ void qnet_policy_step_n(const QRollout& R, Env (&e)[N
 
 // Observation of env i (or zeros past n) into its fp32 tile row; returns live.
 __device__ __forceinline__ bool qnet_load_env(const QRollout& R, int64_t i, Env& e, float* row) {
+  const mg_params& P = R.P;
   double o[kObs];
   const bool live = i < R.n;
   if (live) {
     e = load_env(R.S, i);
     double x1, y1, x2, y2;
-    lon2coord(R.P, e.p1, true, x1, y1);
-    lon2coord(R.P, e.p2, false, x2, y2);
-    observe(R.P, e.p1, e.v1, e.p2, e.v2, x1, y1, x2, y2, o);
+    lon2coord(P, e.p1, true, x1, y1);
+    lon2coord(P, e.p2, false, x2, y2);
+    observe(P, e.p1, e.v1, e.p2, e.v2, x1, y1, x2, y2, o);
   } else {  // a defined state for the lockstep step, which also steps envs past n (never stored)
-    e.p1 = e.p2 = R.P.start_point;
-    e.v1 = e.v2 = R.P.start_vel;
+    e.p1 = e.p2 = P.start_point;
+    e.v1 = e.v2 = P.start_vel;
     e.ret1 = e.ret2 = 0.0;
     e.steps = 0;
     e.winner = 0;
@@ -268,13 +274,9 @@ __device__ __forceinline__ bool qnet_load_env(const QRollout& R, int64_t i, Env&
 #pragma unroll
     for (int k = 0; k < kObs; ++k) o[k] = 0.0;
   }
-  float2* t2 = reinterpret_cast<float2*>(row);
-#pragma unroll
-  for (int k = 0; k < kObs / 2; ++k)
-    t2[k] = make_float2(static_cast<float>(o[2 * k]), static_cast<float>(o[2 * k + 1]));
+  put_obs_row(row, o);
   return live;
 }
-
 
 // The same T steps with the waves specialised: waves 0-3 run only the Q-net (matrix cores +
 // ReLU), waves 4-7 only the fp64 env step, so each SIMD pairs a matrix-heavy wave with a
@@ -302,23 +304,220 @@ __device__ __forceinline__ void qws_wait(const int* flag, int p) {
   while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != p) __builtin_amdgcn_s_sleep(1);
 }
 
+// ---- the Q-net waves' phase Q(X, t) with a net opponent, one function per mode: the forwards of
+// group X's envs on the state step t acts on (wave = threadIdx.x / 64 < 4).
+
+// OPP 2: the tile row of item e of Q-net wave w's list, in the group whose rows begin at gb
+__device__ __forceinline__ int qws2_row(int gb, int w, int e) { return gb + (4 * ((e >> 6) & 1) + w) * 64 + (e & 63); }
+
+// OPP 2, after a forward: the lanes that hold an item (on) write its greedy byte, and the ego's
+// q[0..4] into the env's row, after every read of that row (the opponent items come first)
+__device__ __forceinline__ void qws2_put(const float (&q)[8], int out_dim, bool on, int e, int gb, int w,
+                                         uint8_t* greedy0, uint8_t* greedy1, float* tile) {
+  if (!on) return;
+  const int row = qws2_row(gb, w, e);
+  const uint8_t a = static_cast<uint8_t>(argmax_first(q, out_dim));
+  if (e & 0x80) {
+    greedy1[row] = a;
+  } else {
+    greedy0[row] = a;
+    put_q_row(tile + row * kObs, q);
+  }
+}
+
+// OPP 2 (self-play). Only the forwards the reference evaluates (round 5): choose_action runs the
+// net on its greedy branch only (main.py:105-107), and :221 evaluates it on an episode's last step.
+// The wave's 128 envs of the group are compacted by their need bits into one list, the opponent's
+// items (swapped view) first, and run through the forward 64 at a time on col_tiles(count) column
+// tiles. list / stage / qt: this wave's qlist, qstage ([h][item]) and qtail.
+__device__ __forceinline__ void qws_q_selfplay(const QRollout& R, const uint8_t* lds_net, float* tile,
+                                               uint8_t* greedy0, uint8_t* greedy1, uint8_t* list, u32x4* stage,
+                                               int (&qt)[4], int p) {
+  static_assert(kQWsTiles == 2, "the list holds the wave's two 64-env tiles");
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int gb = (p & 1) * kQWsHalf;
+  const int nb0 = greedy1[qws2_row(gb, wave, lane)], nb1 = greedy1[qws2_row(gb, wave, 64 + lane)];
+  const uint64_t mo0 = __ballot(nb0 & 2), mo1 = __ballot(nb1 & 2);
+  const uint64_t me0 = __ballot(nb0 & 1), me1 = __ballot(nb1 & 1);
+  const int Lo0 = __popcll(mo0), Lo = Lo0 + __popcll(mo1);
+  const int Le0 = __popcll(me0), Ln = Lo + Le0 + __popcll(me1);
+  if (nb0 & 2) list[lane_rank(mo0)] = static_cast<uint8_t>(0x80 | lane);
+  if (nb1 & 2) list[Lo0 + lane_rank(mo1)] = static_cast<uint8_t>(0x80 | 64 | lane);
+  if (nb0 & 1) list[Lo + lane_rank(me0)] = static_cast<uint8_t>(lane);
+  if (nb1 & 1) list[Lo + Le0 + lane_rank(me1)] = static_cast<uint8_t>(64 | lane);
+  {
+    // the same net for both views: stage every item's fragments from its env's lane (both
+    // views of the row from one read), then run the whole list 64 items per forward
+    auto put = [&](int row, int nb, int po, int pe) __attribute__((always_inline)) {
+      float f[kObs];
+#pragma unroll
+      for (int k = 0; k < kObs / 2; ++k) {
+        const f32x2 t2 = reinterpret_cast<const f32x2*>(tile + row * kObs)[k];
+        f[2 * k] = t2[0];
+        f[2 * k + 1] = t2[1];
+      }
+      auto pk = [](float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2)); };
+      if (nb & 2) {  // the opponent's view state[5:] + state[:5] (main.py:199)
+        stage[po] = u32x4{pk(f[5], f[6]), pk(f[7], f[8]), pk(f[9], f[0]), pk(f[1], f[2])};
+        stage[256 + po] = u32x4{pk(f[3], f[4]), 0u, 0x3F800000u, 0x3F803F80u};
+      }
+      if (nb & 1) {
+        stage[pe] = u32x4{pk(f[0], f[1]), pk(f[2], f[3]), pk(f[4], f[5]), pk(f[6], f[7])};
+        stage[256 + pe] = u32x4{pk(f[8], f[9]), 0u, 0x3F800000u, 0x3F803F80u};
+      }
+    };
+    put(qws2_row(gb, wave, lane), nb0, lane_rank(mo0), Lo + lane_rank(me0));
+    put(qws2_row(gb, wave, 64 + lane), nb1, Lo0 + lane_rank(mo1), Lo + Le0 + lane_rank(me1));
+  }
+  wave_lds_sync();
+  const int nq = qws_own_items(Ln);
+  qws_publish_tail(qt, p, nq, Ln, 0);
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll 1
+  for (int c0 = 0; c0 < nq;) {
+    // staged fragments, any mix of views (a view chosen per lane by selects on the features
+    // cost +35 % per launch, r05f q1 / q2)
+    const int cnt = nq - c0 < 64 ? nq - c0 : 64;
+    auto input = [&](int it) __attribute__((always_inline)) {
+      return __builtin_bit_cast(bf16x8, stage[256 * h + c0 + (it < cnt ? it : 0)]);
+    };
+    const int e_out = list[c0 + (lane < cnt ? lane : 0)];  // read ahead: its wait hides under the forward
+    float q[8];
+    qnet_mlp_swp_nc(lds_net, input(r), input(32 + r), q, col_tiles(cnt));
+    qws2_put(q, R.out_dim, lane < cnt, e_out, gb, wave, greedy0, greedy1, tile);
+    wave_lds_sync();
+    c0 += cnt;
+  }
+}
+
+// OPP 3, after the forward over items c0 .. c0 + cnt of a list of nn whose may-finish items are the
+// first nf (an opponent wave) or the last nf (an ego wave): the greedy byte; an opponent wave then
+// publishes the phase in *rows_read once a forward has consumed the may-finish rows, and an ego
+// wave waits for that before it writes its may-finish items' Q rows.
+__device__ __forceinline__ void qws3_put(const float (&q)[8], int out_dim, bool oppw, int c0, int cnt, int nn, int nf,
+                                         int p, int* rows_read, uint8_t* gbyte, float* qrow) {
+  const int lane = threadIdx.x & 63;
+  if (lane < cnt) *gbyte = static_cast<uint8_t>(argmax_first(q, out_dim));
+  if (oppw) {
+    if (c0 < nf && c0 + cnt >= nf && lane == 0) __hip_atomic_store(rows_read, p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else if (c0 + cnt > nn - nf) {
+    qws_wait(rows_read, p);
+    if (lane < cnt && c0 + lane >= nn - nf) put_q_row(qrow, q);
+  }
+}
+
+// OPP 3 (the opponent's own net). Only the forwards the reference evaluates (round 5; OPP 2 above
+// for the common part), with the waves split by net: waves 0-1 run the opponent's net, 2-3 the
+// ego's, each over 256 of the group's 512 envs (rows rb + e). One net per wave keeps the view
+// uniform and gives each wave ~194 items = three full 64-item forwards and a narrow one; split by
+// env instead, each wave ran both nets on ~97 items apiece (two forwards per net, the second three
+// tiles wide). An ego wave writes eval_net(state)[0..4] into the tile rows of its may-finish items
+// only (an episode can end only there, main.py:221) and only once the opponent wave of the same
+// rows has read them: that wave lists those items first and publishes the phase in qrows_read[hw]
+// after their forward; the ego wave lists them last.
+__device__ __forceinline__ void qws_q_split(const QRollout& R, const uint8_t* lds_net, const uint8_t* lds_net2,
+                                            float* tile, uint8_t* greedy0, uint8_t* greedy1, uint8_t* list,
+                                            int (&qt)[4], int* qrows_read, int p) {
+  static_assert(kQWsHalf == 512, "two waves per net, 256 envs each");
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool oppw = wave < 2;
+  const int hw = wave & 1;
+  const int rb = (p & 1) * kQWsHalf + 256 * hw;
+  uint8_t* gout = (oppw ? greedy1 : greedy0) + rb;
+  uint64_t mn[4], mf[4];
+  int nn = 0, nf = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int nb = gout[64 * k + lane];
+    mn[k] = __ballot(nb & 1);
+    mf[k] = __ballot((nb & 3) == 3);
+    nn += __popcll(mn[k]);
+    nf += __popcll(mf[k]);
+  }
+  int of = oppw ? 0 : nn - nf, on = oppw ? nf : 0;  // may-finish items first / last
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint64_t mo = mn[k] & ~mf[k];
+    if ((mf[k] >> lane) & 1)
+      list[of + lane_rank(mf[k])] = static_cast<uint8_t>(64 * k + lane);
+    else if ((mo >> lane) & 1)
+      list[on + lane_rank(mo)] = static_cast<uint8_t>(64 * k + lane);
+    of += __popcll(mf[k]);
+    on += __popcll(mo);
+  }
+  wave_lds_sync();
+  const int nq = qws_own_items(nn);
+  qws_publish_tail(qt, p, nq, nn, nf);
+  if (oppw && nf == 0 && lane == 0) __hip_atomic_store(&qrows_read[hw], p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  const int r = lane & 31, h = lane >> 5;
+  const uint8_t* net = oppw ? lds_net2 : lds_net;
+  // the tile rows of a chunk's items (column envs r and 32 + r, and this lane's result row),
+  // read one chunk ahead: a forward's inputs then wait for one LDS read, not two
+  auto rows_of = [&](int c, int& ra, int& rc, int& ro) __attribute__((always_inline)) {
+    const int n = nn - c < 64 ? nn - c : 64;
+    ra = rb + list[c + (r < n ? r : 0)];
+    rc = rb + list[c + (32 + r < n ? 32 + r : 0)];
+    ro = rb + list[c + (lane < n ? lane : 0)];
+  };
+  int ra, rc, row;
+  rows_of(0, ra, rc, row);
+#pragma unroll 1
+  for (int c0 = 0; c0 < nq;) {
+    const int cnt = nq - c0 < 64 ? nq - c0 : 64;
+    auto input = [&](int j) __attribute__((always_inline)) {
+      const float* rw = tile + j * kObs;
+      return oppw ? qnet_input(rw, true, h) : qnet_input(rw, false, h);
+    };
+    const bf16x8 x0 = input(ra), x1 = input(rc);
+    const int rcur = row;
+    if (c0 + cnt < nq) rows_of(c0 + cnt, ra, rc, row);
+    float q[8];
+    qnet_mlp_swp_nc(net, x0, x1, q, col_tiles(cnt));
+    // (nf > nq: the env wave running the tail publishes the phase)
+    qws3_put(q, R.out_dim, oppw, c0, cnt, nn, nf, p, &qrows_read[hw], gout + (rcur - rb), tile + rcur * kObs);
+    wave_lds_sync();
+    c0 += cnt;
+  }
+}
+
+// OPP 2 / 3, env wave ew: Q-net wave ew's list tail for Q(group p & 1, step p / 2) -- its 1..16
+// items past three full forwards, one column tile -- as that wave would run it (qtail).
 template <int OPP>
-constexpr int qws_ilp() { return kQWsIlp; }
-template <int OPP>
-constexpr int qws_envs() { return 2 * 64 * kQWsEnvWaves * qws_ilp<OPP>(); }
+__device__ __forceinline__ void qws_env_tail(const QRollout& R, const uint8_t* lds_net, const uint8_t* lds_net2,
+                                             float* tile, uint8_t* greedy0, uint8_t* greedy1, const uint8_t* list,
+                                             const u32x4* stage, const int (&qt)[4], int* qrows_read, int p, int ew) {
+  qws_wait(&qt[0], p);
+  const int nq = qt[1], nn = qt[2];
+  if (nn <= nq) return;
+  const int cnt = nn - nq;
+  const int lane = threadIdx.x & 63, r32 = lane & 31, h = lane >> 5;
+  const int it = nq + (r32 < cnt ? r32 : 0), io = nq + (lane < cnt ? lane : 0);
+  float q[8];
+  if constexpr (OPP == 3) {
+    const bool oppw = ew < 2;
+    const int hw = ew & 1, nf = qt[3];
+    const int rb = (p & 1) * kQWsHalf + 256 * hw;
+    const float* rw = tile + (rb + list[it]) * kObs;
+    const int row = rb + list[io];
+    const bf16x8 x = oppw ? qnet_input(rw, true, h) : qnet_input(rw, false, h);
+    qnet_mlp<2 * kQLdsAhead, 1>(qnet_lds(oppw ? lds_net2 : lds_net), x, x, q);
+    qws3_put(q, R.out_dim, oppw, nq, cnt, nn, nf, p, &qrows_read[hw], (oppw ? greedy1 : greedy0) + row,
+             tile + row * kObs);
+  } else {
+    const bf16x8 x = __builtin_bit_cast(bf16x8, stage[256 * h + it]);
+    qnet_mlp<2 * kQLdsAhead, 1>(qnet_lds(lds_net), x, x, q);
+    qws2_put(q, R.out_dim, lane < cnt, list[io], (p & 1) * kQWsHalf, ew, greedy0, greedy1, tile);
+  }
+}
 
 // CHECKED: a greedy action may fall outside action_dict (a net with out_dim > 5): the lockstep step
 // carries the KeyError selects. Every other launch takes CHECKED = false (-2 % on the ego-only
 // leg, r03i; the self-play and other-net instances showed no gain and keep the checked step).
 template <int OPP, bool CHECKED>
 __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws_kernel(const QRollout R) {
-  constexpr int kIlp = qws_ilp<OPP>();
-  constexpr int kEnvs = qws_envs<OPP>();  // envs per block
-  constexpr int kHalf = kEnvs / 2;        // envs per group
-  constexpr int kTiles = kHalf / 256;     // 64-env tiles each Q-net wave computes per phase
-  constexpr int kEnvWaves = kQWsEnvWaves;
-  static_assert(kTiles >= 1 && kHalf == 64 * kEnvWaves * kIlp && kHalf % 256 == 0,
-                "group = 4 Q-net waves x kTiles x 64 envs = env waves x ILP x 64 envs");
+  constexpr int kIlp = kQWsIlp;
+  constexpr int kEnvs = kQWsEnvs;  // envs per block
+  constexpr int kHalf = kQWsHalf;  // envs per group
   // OPP 0 / 1: the 32x32 layout (second part of the packed buffer) and forward, see qnet32_mlp
   constexpr bool kNet32 = OPP < 2;
   __shared__ __attribute__((aligned(16))) uint8_t lds_net[kNet32 ? kQ32NetBytes : kQNetBytes];
@@ -347,7 +546,6 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t base = static_cast<int64_t>(blockIdx.x) * kEnvs;
-  const bool qwave = wave < 4;
   const int ew = wave - 4;
 
   if constexpr (kNet32) {
@@ -360,204 +558,29 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
   if (tid < 2) qrows_read[tid] = -1;
   if (OPP >= 2 && tid < 4) qtail[tid][0] = -1;
   const int phases = 2 * R.num_steps + 1;
-  if (qwave) {
+  if (wave < 4) {
     // Q-net waves: the barrier count matches the env waves' loop below, phase for phase
     // (roles are whole waves, so s_barrier pairs up; the two loops keep each role's live
     // registers apart -- in one loop the env state sat beside the accumulators and spilled)
     __syncthreads();
     for (int p = 0; p < phases; ++p) {
-      if constexpr (OPP == 3) {
-        // Only the forwards the reference evaluates (round 5; OPP 2 below for the common part), with
-        // the waves split by net: waves 0-1 run the opponent's net, 2-3 the ego's, each over 256 of
-        // the group's 512 envs (rows rb + e). One net per wave keeps the view uniform and gives each
-        // wave ~194 items = three full 64-item forwards and a narrow one; split by env instead, each
-        // wave ran both nets on ~97 items apiece (two forwards per net, the second three tiles wide).
-        // An ego wave writes eval_net(state)[0..4] into the tile rows of its may-finish items only (an
-        // episode can end only there, main.py:221) and only once the opponent wave of the same rows
-        // has read them: that wave lists those items first and publishes the phase in
-        // qrows_read[hw] after their forward; the ego wave lists them last.
-        if (p < 2 * R.num_steps) {
-          static_assert(kHalf == 512, "two waves per net, 256 envs each");
-          const bool oppw = wave < 2;
-          const int hw = wave & 1;
-          const int rb = (p & 1) * kHalf + 256 * hw;
-          uint8_t* gout = greedy[oppw ? 1 : 0] + rb;
-          uint8_t* list = qlist[wave];
-          uint64_t mn[4], mf[4];
-          int nn = 0, nf = 0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int nb = gout[64 * k + lane];
-            mn[k] = __ballot(nb & 1);
-            mf[k] = __ballot((nb & 3) == 3);
-            nn += __popcll(mn[k]);
-            nf += __popcll(mf[k]);
-          }
-          int of = oppw ? 0 : nn - nf, on = oppw ? nf : 0;  // may-finish items first / last
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const uint64_t mo = mn[k] & ~mf[k];
-            if ((mf[k] >> lane) & 1)
-              list[of + lane_rank(mf[k])] = static_cast<uint8_t>(64 * k + lane);
-            else if ((mo >> lane) & 1)
-              list[on + lane_rank(mo)] = static_cast<uint8_t>(64 * k + lane);
-            of += __popcll(mf[k]);
-            on += __popcll(mo);
-          }
-          wave_lds_sync();
-          const int nq = qws_own_items(nn);
-          qws_publish_tail(qtail[wave], p, nq, nn, nf);
-          if (oppw && nf == 0 && lane == 0) __hip_atomic_store(&qrows_read[hw], p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-          const int fin0 = nn - nf;  // an ego wave's first may-finish item
-          const int r = lane & 31, h = lane >> 5;
-          const uint8_t* net = oppw ? lds_net2 : lds_net;
-          // the tile rows of a chunk's items (column envs r and 32 + r, and this lane's result row),
-          // read one chunk ahead: a forward's inputs then wait for one LDS read, not two
-          auto rows_of = [&](int c, int& ra, int& rc, int& ro) __attribute__((always_inline)) {
-            const int n = nn - c < 64 ? nn - c : 64;
-            ra = rb + list[c + (r < n ? r : 0)];
-            rc = rb + list[c + (32 + r < n ? 32 + r : 0)];
-            ro = rb + list[c + (lane < n ? lane : 0)];
-          };
-          int ra, rc, row;
-          rows_of(0, ra, rc, row);
-#pragma unroll 1
-          for (int c0 = 0; c0 < nq;) {
-            const int cnt = nq - c0 < 64 ? nq - c0 : 64;
-            auto input = [&](int j) __attribute__((always_inline)) {
-              const float* rw = tile + j * kObs;
-              return oppw ? qnet_input(rw, true, h) : qnet_input(rw, false, h);
-            };
-            const bf16x8 x0 = input(ra), x1 = input(rc);
-            const int rcur = row;
-            if (c0 + cnt < nq) rows_of(c0 + cnt, ra, rc, row);
-            float q[8];
-            qnet_mlp_swp_nc(net, x0, x1, q, col_tiles(cnt));
-            if (lane < cnt) gout[rcur - rb] = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-            if (oppw) {  // (nf > nq: the env wave running the tail publishes it)
-              if (c0 < nf && c0 + cnt >= nf && lane == 0)  // the forward has consumed its rows
-                __hip_atomic_store(&qrows_read[hw], p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else if (c0 + cnt > fin0) {
-              qws_wait(&qrows_read[hw], p);
-              if (lane < cnt && c0 + lane >= fin0) {
-                float* qr = tile + rcur * kObs;
-                reinterpret_cast<f32x2*>(qr)[0] = f32x2{q[0], q[1]};
-                reinterpret_cast<f32x2*>(qr)[1] = f32x2{q[2], q[3]};
-                qr[4] = q[4];
-              }
-            }
-            wave_lds_sync();
-            c0 += cnt;
-          }
-        }
-        __syncthreads();
-        continue;
-      }
-      if constexpr (OPP == 2) {
-        // Only the forwards the reference evaluates (round 5): choose_action runs the net on its
-        // greedy branch only (main.py:105-107), and :221 evaluates it on an episode's last step.
-        // The wave's 128 envs of the group are compacted by their need bits into one list, the
-        // opponent's items (swapped view) first, and each view's items run through the forward 64
-        // at a time on col_tiles(count) column tiles. The ego's q[0..4] go into the env's tile row
-        // for q_eval, after every read of that row (the opponent items come first).
-        if (p < 2 * R.num_steps) {
-          static_assert(kTiles == 2, "the list holds the wave's two 64-env tiles");
-          const int gb = (p & 1) * kHalf;
-          auto row_of = [&](int e) __attribute__((always_inline)) { return gb + (4 * ((e >> 6) & 1) + wave) * 64 + (e & 63); };
-          uint8_t* list = qlist[wave];
-          const int nb0 = greedy[1][row_of(lane)], nb1 = greedy[1][row_of(64 + lane)];
-          const uint64_t mo0 = __ballot(nb0 & 2), mo1 = __ballot(nb1 & 2);
-          const uint64_t me0 = __ballot(nb0 & 1), me1 = __ballot(nb1 & 1);
-          const int Lo0 = __popcll(mo0), Lo = Lo0 + __popcll(mo1);
-          const int Le0 = __popcll(me0), Ln = Lo + Le0 + __popcll(me1);
-          if (nb0 & 2) list[lane_rank(mo0)] = static_cast<uint8_t>(0x80 | lane);
-          if (nb1 & 2) list[Lo0 + lane_rank(mo1)] = static_cast<uint8_t>(0x80 | 64 | lane);
-          if (nb0 & 1) list[Lo + lane_rank(me0)] = static_cast<uint8_t>(lane);
-          if (nb1 & 1) list[Lo + Le0 + lane_rank(me1)] = static_cast<uint8_t>(64 | lane);
-          {
-            // the same net for both views: stage every item's fragments from its env's lane (both
-            // views of the row from one read), then run the whole list 64 items per forward
-            auto stage = [&](int row, int nb, int po, int pe) __attribute__((always_inline)) {
-              float f[kObs];
-#pragma unroll
-              for (int k = 0; k < kObs / 2; ++k) {
-                const f32x2 t2 = reinterpret_cast<const f32x2*>(tile + row * kObs)[k];
-                f[2 * k] = t2[0];
-                f[2 * k + 1] = t2[1];
-              }
-              auto pk = [](float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2)); };
-              if (nb & 2) {  // the opponent's view state[5:] + state[:5] (main.py:199)
-                qstage[wave][0][po] = u32x4{pk(f[5], f[6]), pk(f[7], f[8]), pk(f[9], f[0]), pk(f[1], f[2])};
-                qstage[wave][1][po] = u32x4{pk(f[3], f[4]), 0u, 0x3F800000u, 0x3F803F80u};
-              }
-              if (nb & 1) {
-                qstage[wave][0][pe] = u32x4{pk(f[0], f[1]), pk(f[2], f[3]), pk(f[4], f[5]), pk(f[6], f[7])};
-                qstage[wave][1][pe] = u32x4{pk(f[8], f[9]), 0u, 0x3F800000u, 0x3F803F80u};
-              }
-            };
-            stage(row_of(lane), nb0, lane_rank(mo0), Lo + lane_rank(me0));
-            stage(row_of(64 + lane), nb1, Lo0 + lane_rank(mo1), Lo + Le0 + lane_rank(me1));
-          }
-          wave_lds_sync();
-          const int nq = qws_own_items(Ln);
-          qws_publish_tail(qtail[wave], p, nq, Ln, 0);
-          const int r = lane & 31, h = lane >> 5;
-#pragma unroll 1
-          for (int c0 = 0; c0 < nq;) {
-            // staged fragments, any mix of views (a view chosen per lane by selects on the features
-            // cost +35 % per launch, r05f q1 / q2)
-            const int cnt = nq - c0 < 64 ? nq - c0 : 64;
-            auto input = [&](int it) __attribute__((always_inline)) {
-              return __builtin_bit_cast(bf16x8, qstage[wave][h][c0 + (it < cnt ? it : 0)]);
-            };
-            const int e_out = list[c0 + (lane < cnt ? lane : 0)];  // read ahead: its wait hides under the forward
-            float q[8];
-            qnet_mlp_swp_nc(lds_net, input(r), input(32 + r), q, col_tiles(cnt));
-            if (lane < cnt) {
-              const int e = e_out;
-              const int row = row_of(e);
-              const uint8_t a = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-              if (e & 0x80) {
-                greedy[1][row] = a;
-              } else {
-                greedy[0][row] = a;
-                // eval_net(state)[0..4] into the row the env wave reads at an episode end (main.py:221)
-                float* qr = tile + row * kObs;
-                reinterpret_cast<f32x2*>(qr)[0] = f32x2{q[0], q[1]};
-                reinterpret_cast<f32x2*>(qr)[1] = f32x2{q[2], q[3]};
-                qr[4] = q[4];
-              }
-            }
-            wave_lds_sync();
-            c0 += cnt;
-          }
-        }
-        __syncthreads();
-        continue;
-      }
       if (p < 2 * R.num_steps) {
+        if constexpr (OPP == 3)
+          qws_q_split(R, lds_net, lds_net2, tile, greedy[0], greedy[1], qlist[wave], qtail[wave],
+                      qrows_read, p);
+        else if constexpr (OPP == 2)
+          qws_q_selfplay(R, lds_net, tile, greedy[0], greedy[1], qlist[wave], &qstage[wave][0][0],
+                         qtail[wave], p);
+        else  // OPP 0 / 1: the 32x32 forward over each of the wave's 64-env tiles of the group
 #pragma unroll 1
-        for (int tt = 0; tt < kTiles; ++tt) {
-          const int row0 = (p & 1) * kHalf + (4 * tt + wave) * 64;
-          float q[8];
-          if constexpr (OPP >= 2) {  // the opponent's view state[5:] + state[:5] (main.py:199)
-            qnet_forward_swp(OPP == 3 ? lds_net2 : lds_net, tile, row0, true, q);
-            greedy[1][row0 + lane] = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-          }
-          if constexpr (kNet32)
+          for (int tt = 0; tt < kQWsTiles; ++tt) {
+            const int row0 = (p & 1) * kHalf + (4 * tt + wave) * 64;
+            float q[8];
             qnet32_forward(lds_net, tile, row0, false, q);
-          else
-            qnet_forward_swp(lds_net, tile, row0, false, q);
-          greedy[0][row0 + lane] = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-          // eval_net(state)[0..4] into the env's tile row, whose observation both forwards have
-          // read (the MFMA chain behind q waits for every read): the env wave steps the env in the
-          // next phase and logs q[action] when the episode ends (main.py:221), before it writes
-          // the next observation into the row
-          float* qr = tile + (row0 + lane) * kObs;
-          reinterpret_cast<f32x2*>(qr)[0] = f32x2{q[0], q[1]};
-          reinterpret_cast<f32x2*>(qr)[1] = f32x2{q[2], q[3]};
-          qr[4] = q[4];
-        }
+            greedy[0][row0 + lane] = static_cast<uint8_t>(argmax_first(q, R.out_dim));
+            // the row's observation has been read: the MFMA chain behind q waits for every read
+            put_q_row(tile + (row0 + lane) * kObs, q);
+          }
       }
       __syncthreads();
     }
@@ -585,8 +608,8 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
         o0[k] = tile[la * kObs + k];
         o1[k] = tile[lb * kObs + k];
       }
-      un0[j] = qnet_draws(R, base + la, R.first_step);
-      un1[j] = qnet_draws(R, base + lb, R.first_step);
+      un0[j] = philox_env_step(static_cast<uint64_t>(R.env_offset + base + la), R.first_step, R.seed);
+      un1[j] = philox_env_step(static_cast<uint64_t>(R.env_offset + base + lb), R.first_step, R.seed);
       qnet_put_need<OPP>(&greedy[0][la], &greedy[1][la], qnet_need_bits(R, un0[j], live0[j], e0[j], o0));
       qnet_put_need<OPP>(&greedy[0][lb], &greedy[1][lb], qnet_need_bits(R, un1[j], live1[j], e1[j], o1));
     }
@@ -629,56 +652,9 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
                              wrows);
     }
     if constexpr (OPP >= 2) {
-      // Q-net wave ew's list tail for Q(group p & 1, step p / 2), as that wave would run it (qtail)
-      if (p < 2 * R.num_steps) {
-        qws_wait(&qtail[ew][0], p);
-        const int nq = qtail[ew][1], nn = qtail[ew][2];
-        if (nn > nq) {
-          const int cnt = nn - nq;  // 1..16: one column tile
-          const uint8_t* list = qlist[ew];
-          const int r32 = lane & 31, h = lane >> 5;
-          const int it = nq + (r32 < cnt ? r32 : 0), io = nq + (lane < cnt ? lane : 0);
-          float q[8];
-          if constexpr (OPP == 3) {
-            const bool oppw = ew < 2;
-            const int hw = ew & 1, nf = qtail[ew][3];
-            const int rb = (p & 1) * kHalf + 256 * hw;
-            const float* rw = tile + (rb + list[it]) * kObs;
-            const int row = rb + list[io];
-            const bf16x8 x = oppw ? qnet_input(rw, true, h) : qnet_input(rw, false, h);
-            qnet_mlp<2 * kQLdsAhead, 1>(qnet_lds(oppw ? lds_net2 : lds_net), x, x, q);
-            if (lane < cnt) greedy[oppw ? 1 : 0][row] = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-            if (oppw) {
-              if (nf > nq && lane == 0) __hip_atomic_store(&qrows_read[hw], p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else if (nn - nf < nn) {  // may-finish items, listed last
-              qws_wait(&qrows_read[hw], p);
-              if (lane < cnt && io >= nn - nf) {
-                float* qr = tile + row * kObs;
-                reinterpret_cast<f32x2*>(qr)[0] = f32x2{q[0], q[1]};
-                reinterpret_cast<f32x2*>(qr)[1] = f32x2{q[2], q[3]};
-                qr[4] = q[4];
-              }
-            }
-          } else {
-            const bf16x8 x = __builtin_bit_cast(bf16x8, qstage[ew][h][it]);
-            qnet_mlp<2 * kQLdsAhead, 1>(qnet_lds(lds_net), x, x, q);
-            if (lane < cnt) {
-              const int e = list[io];
-              const int row = (p & 1) * kHalf + (4 * ((e >> 6) & 1) + ew) * 64 + (e & 63);
-              const uint8_t a = static_cast<uint8_t>(argmax_first(q, R.out_dim));
-              if (e & 0x80) {
-                greedy[1][row] = a;
-              } else {
-                greedy[0][row] = a;
-                float* qr = tile + row * kObs;
-                reinterpret_cast<f32x2*>(qr)[0] = f32x2{q[0], q[1]};
-                reinterpret_cast<f32x2*>(qr)[1] = f32x2{q[2], q[3]};
-                qr[4] = q[4];
-              }
-            }
-          }
-        }
-      }
+      if (p < 2 * R.num_steps)
+        qws_env_tail<OPP>(R, lds_net, lds_net2, tile, greedy[0], greedy[1], qlist[ew], &qstage[OPP == 2 ? ew : 0][0][0],
+                          qtail[ew], qrows_read, p, ew);
     }
     __syncthreads();
   }

@@ -20,13 +20,18 @@ __device__ __forceinline__ void wave_lds_sync() {
 // new observations afterwards, and no other wave is waited for (no block barrier).
 __device__ __forceinline__ void wave_copy_rows(const float* wtile, float* dst, int nrows);
 
-__device__ __forceinline__ void wave_store_obs(float* wtile, const obs_t (&o)[kObs], float* dst,
-                                               int nrows) {
-  const int lane = threadIdx.x & 63;
-  float2* t2 = reinterpret_cast<float2*>(wtile + lane * kObs);
+// One observation (fp64, or a step's obs_t) as the fp32 row of an LDS tile, in 8-byte pieces.
+template <class T>
+__device__ __forceinline__ void put_obs_row(float* row, const T (&o)[kObs]) {
+  float2* t2 = reinterpret_cast<float2*>(row);
 #pragma unroll
   for (int k = 0; k < kObs / 2; ++k)
     t2[k] = make_float2(static_cast<float>(o[2 * k]), static_cast<float>(o[2 * k + 1]));
+}
+
+__device__ __forceinline__ void wave_store_obs(float* wtile, const obs_t (&o)[kObs], float* dst,
+                                               int nrows) {
+  put_obs_row(wtile + (threadIdx.x & 63) * kObs, o);
   wave_lds_sync();
   wave_copy_rows(wtile, dst, nrows);
   wave_lds_sync();
@@ -39,12 +44,7 @@ __device__ __forceinline__ void wave_store_obs_n(float* wtile, const StepOut (&r
                                                  int nrows) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    float2* t2 = reinterpret_cast<float2*>(wtile + (64 * j + lane) * kObs);
-#pragma unroll
-    for (int k = 0; k < kObs / 2; ++k)
-      t2[k] = make_float2(static_cast<float>(r[j].o[2 * k]), static_cast<float>(r[j].o[2 * k + 1]));
-  }
+  for (int j = 0; j < N; ++j) put_obs_row(wtile + (64 * j + lane) * kObs, r[j].o);
   wave_lds_sync();
   wave_copy_rows(wtile, dst, nrows);
   wave_lds_sync();

@@ -25,31 +25,22 @@ extern "C" int mg_debug_clocks(void* dst) { return hipMemcpyFromSymbol(dst, HIP_
 Q5_EDITS = [
     ("""    __syncthreads();
     for (int p = 0; p < phases; ++p) {
-      if constexpr (OPP == 3) {""",
+      if (p < 2 * R.num_steps) {""",
      """    __syncthreads();
     for (int p = 0; p < phases; ++p) {
       MG_CLK(0);
-      int fidx = 0;
-      if constexpr (OPP == 3) {"""),
-    ("""        __syncthreads();
-        continue;
-      }""",
-     """        MG_CLK(1);
-        __syncthreads();
-        continue;
-      }""", 2),
-    ("""            qnet_mlp_swp_nc(net, input(r), input(32 + r), q, col_tiles(cnt));""",
-     """            if (fidx < 6) MG_CLK(2 + fidx);
-            qnet_mlp_swp_nc(net, input(r), input(32 + r), q, col_tiles(cnt));
-            asm volatile("" :: "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[4]));
-            if (fidx < 6) MG_CLK(8 + fidx);
-            ++fidx;"""),
-    ("""            qnet_mlp_swp_nc((OPP == 3 && opp) ? lds_net2 : lds_net, input(r), input(32 + r), q, col_tiles(cnt));""",
-     """            if (fidx < 6) MG_CLK(2 + fidx);
-            qnet_mlp_swp_nc((OPP == 3 && opp) ? lds_net2 : lds_net, input(r), input(32 + r), q, col_tiles(cnt));
-            asm volatile("" :: "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[4]));
-            if (fidx < 6) MG_CLK(8 + fidx);
-            ++fidx;"""),
+      if (p < 2 * R.num_steps) {"""),
+    # the list forwards of qws_q_selfplay and qws_q_split: chunk c0 / 64 is the phase's k-th forward
+    ("""    qnet_mlp_swp_nc(lds_net, input(r), input(32 + r), q, col_tiles(cnt));""",
+     """    if (c0 < 384) MG_CLK(2 + (c0 >> 6));
+    qnet_mlp_swp_nc(lds_net, input(r), input(32 + r), q, col_tiles(cnt));
+    asm volatile("" :: "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[4]));
+    if (c0 < 384) MG_CLK(8 + (c0 >> 6));"""),
+    ("""    qnet_mlp_swp_nc(net, x0, x1, q, col_tiles(cnt));""",
+     """    if (c0 < 384) MG_CLK(2 + (c0 >> 6));
+    qnet_mlp_swp_nc(net, x0, x1, q, col_tiles(cnt));
+    asm volatile("" :: "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[4]));
+    if (c0 < 384) MG_CLK(8 + (c0 >> 6));"""),
 ]
 Q5_BASE_EDITS = [
     ("""    __syncthreads();
