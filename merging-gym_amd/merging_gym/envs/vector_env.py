@@ -144,6 +144,8 @@ class MergeVecEnv:
         self._stats = _native.Stats(ptr(self._ep_stats))
         self._flags = _native.AUTORESET if self.autoreset else 0
         self._step_idx = 0
+        # rollout_hdqn's carried state (None = none yet: the first launch allocates it) and buffers
+        self.hdqn_goal = self.hdqn_goal_op = self.hdqn_ext = self._hdqn_bufs = None
         # pre-bound call arguments: a step costs one ctypes call and no allocations
         self._p_ref, self._s_ref = ctypes.byref(self.params), ctypes.byref(self._state)
         self._o_ref, self._st_ref = ctypes.byref(self._out), ctypes.byref(self._stats)
@@ -226,7 +228,7 @@ class MergeVecEnv:
             self._mask_keepalive = mt
             m = ctypes.c_void_p(mt.data_ptr())
         for name, fresh in (("hdqn_goal", -1), ("hdqn_goal_op", -1), ("hdqn_ext", 0)):
-            t = getattr(self, name, None)
+            t = getattr(self, name)
             if t is not None:
                 if mt is None:
                     t.fill_(fresh)
@@ -414,7 +416,7 @@ class MergeVecEnv:
             raise ValueError("need hdqn.py's nets: meta-net in_dim 10, lower-level Net in_dim 11 -> 5")
         k0 = self._step_idx if first_step is None else int(first_step)
         buf = self._traj(T, final_observation, won_mask)
-        hb = getattr(self, "_hdqn_bufs", None)
+        hb = self._hdqn_bufs
         if hb is None or hb["goal"].shape[0] != T:
             hb = {k: torch.empty((T, n), dtype=torch.float32, device=self.device)
                   for k in ("goal", "next_goal", "reward", "goal_op", "ext_reward")}
@@ -426,20 +428,19 @@ class MergeVecEnv:
         if not self.autoreset:
             raise ValueError("rollout_hdqn runs hdqn.py's loop, which resets every finished episode: "
                              "it needs MergeVecEnv(autoreset=True)")
-        if getattr(self, "hdqn_ext", None) is None:
+        if self.hdqn_ext is None:
             # the extrinsic-reward sums are kept from the first launch on, whether or not this
             # launch returns Goal_DQN's columns, so turning goal_memory on later is consistent
             self.hdqn_ext = torch.zeros(n, dtype=torch.float64, device=self.device)
-        if getattr(self, "hdqn_goal", None) is None:
+        if self.hdqn_goal is None:
             self.hdqn_goal = torch.full((n,), -1, dtype=torch.int8, device=self.device)
-        if mode >= 2 and getattr(self, "hdqn_goal_op", None) is None:
+        if mode >= 2 and self.hdqn_goal_op is None:
             self.hdqn_goal_op = torch.full((n,), -1, dtype=torch.int8, device=self.device)
-        gop = getattr(self, "hdqn_goal_op", None)
-        ext = self.hdqn_ext
+        gop = self.hdqn_goal_op
         rc = nat.lib.mg_rollout_hdqn(
             self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), ctypes.byref(hb["_hm" if goal_memory else "_h"]),
             self._st_ref, self.hdqn_goal.data_ptr(), None if gop is None else gop.data_ptr(),
-            None if ext is None else ext.data_ptr(), n, self.env_offset, seed & 0xFFFFFFFFFFFFFFFF, k0 & 0xFFFFFFFFFFFFFFFF,
+            self.hdqn_ext.data_ptr(), n, self.env_offset, seed & 0xFFFFFFFFFFFFFFFF, k0 & 0xFFFFFFFFFFFFFFFF,
             T, meta.packed.data_ptr(), meta.out_dim, lower.packed.data_ptr(), meta.reset_argmax(self.params),
             greedy_threshold(episilo), mode, None if opp_meta is None else opp_meta.packed.data_ptr(),
             None if opp_lower is None else opp_lower.packed.data_ptr(), None if ring is None else ring.memory.data_ptr(),
@@ -554,11 +555,11 @@ class MergeVecEnv:
         if self.ret_sum is not None:
             sd["episode_stats"] = self._ep_stats.clone()  # the 64-byte records, pending value included
             sd["episode_stats_format"] = self._nat.EPISODE_STATS_FORMAT
-        if getattr(self, "hdqn_goal", None) is not None:
+        if self.hdqn_goal is not None:
             sd["hdqn_goal"] = self.hdqn_goal.clone()  # rollout_hdqn's current goals
-        if getattr(self, "hdqn_goal_op", None) is not None:
+        if self.hdqn_goal_op is not None:
             sd["hdqn_goal_op"] = self.hdqn_goal_op.clone()  # and the self-play opponent's
-        if getattr(self, "hdqn_ext", None) is not None:
+        if self.hdqn_ext is not None:
             sd["hdqn_ext"] = self.hdqn_ext.clone()  # extrinsic reward of the running inner loops
         return sd
 

@@ -80,7 +80,7 @@ def test_rollout_qnet_runs_are_bit_identical(opponent):
     _assert_same(*runs)
 
 
-@pytest.mark.parametrize("opponent", ["self", "other"])
+@pytest.mark.parametrize("opponent", ["self", "other", "uniform"])
 def test_rollout_hdqn_runs_are_bit_identical(opponent):
     from merging_gym.policy import NUM_GOALS, QNet
 
@@ -89,7 +89,7 @@ def test_rollout_hdqn_runs_are_bit_identical(opponent):
     meta = QNet.from_state_dict(_signed(rng, 10, NUM_GOALS), device="cuda:0")
     lower = QNet.from_state_dict(_signed(rng, 11, 5), device="cuda:0")
     opp = ((QNet.from_state_dict(_signed(rng, 10, NUM_GOALS), device="cuda:0"),
-            QNet.from_state_dict(_signed(rng, 11, 5), device="cuda:0")) if opponent == "other" else "self")
+            QNet.from_state_dict(_signed(rng, 11, 5), device="cuda:0")) if opponent == "other" else opponent)
     env = _env(n, seed)
     start = env.state_dict()
     runs = []

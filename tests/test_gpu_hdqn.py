@@ -157,7 +157,7 @@ def _swap(o):
 
 
 @pytest.mark.parametrize("n,opponent", [(2048, "none"), (1000, "none"), (2048, "self"), (1000, "self"),
-                                        (2048, "other"), (1000, "other"), (1000, "self-selector"),
+                                        (2048, "other"), (1000, "other"), (1000, "uniform"), (1000, "self-selector"),
                                         (1000, "other-selector"), (1000, "self-signed"), (1000, "other-signed")])
 def test_fused_hdqn_rollout(coracle, n, opponent):
     """mg_rollout_hdqn -- hdqn.py:280-323 in one launch -- against the loop restated on the CPU:
@@ -170,7 +170,9 @@ def test_fused_hdqn_rollout(coracle, n, opponent):
     epsilon-greedy choice on the swapped state at every outer-loop iteration (:285) and kept in
     between, its action the lower net's on [goal_op] + swapped state (:299-300). opponent
     "other" (any other Strategy_OP, :265-268): the same, with a second pair of nets standing in
-    for the checkpoint load_path_op holds (the kernel reads them from global memory)."""
+    for the checkpoint load_path_op holds (the kernel reads them from global memory). opponent
+    "uniform": no opponent nets; its action is floor(5 z / 2^32) of the fresh-goal stream's word z,
+    exactly, and that stream is drawn once per step instead of once per two."""
     _fused_hdqn_rollout(coracle, n, opponent)
 
 
@@ -229,7 +231,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
     ChoiceCheck("reset goal").check([reset_goal], q_reset.argmax(1), [True], q_reset, q_exact=exact_q(meta_sd, reset_obs))
     fresh_off = -(1 << 63)  # counter (env ^ 2^63, step): the fresh-goal stream
     op_off = 1 << 62  # counter (env ^ 2^62, step): the self-play opponent's stream
-    selfplay = opponent != "none"  # the opponent acts through h-DQN nets
+    selfplay = opponent not in ("none", "uniform")  # the opponent acts through h-DQN nets
     goal_prev = gop_prev = None
     rows = {k: [] for k in ("obs0", "obs", "fobs", "a1", "rew", "done", "goal", "goal2", "r_int")}
     ring = ReplayRing(4 * n * T, device=dev, goal=True)
@@ -246,6 +248,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
         obs_first = obs.copy()
         tr = env.rollout_hdqn(T, meta, lower, seed, opponent=opp_arg, first_step=k0, ring=ring_f, goal_memory=True)
         ring_m.store_meta(tr)
+        assert ("goal_op" in tr) == selfplay
         ext_all = tr["ext_reward"].cpu().numpy().copy()
         nb_all = tr["no_break"].cpu().numpy().copy()
         g = {k: tr[k].cpu().numpy().copy() for k in ("goal", "next_goal", "reward") + (("goal_op",) if selfplay else ())}
@@ -272,12 +275,12 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
                            f"launch {launch} opponent's first goals", q_exact=exact_q(op_meta_sd, _swap(obs)))
             else:
                 assert (g["goal_op"][0] == gop_prev).all(), launch
-        else:
+        elif opponent == "none":
             assert (a2_all == -1).all()
         for t in range(T):
             k = k0 + t
             ua = coracle.philox_batch(n, 0, seed, k)
-            ubx, uby, _ = mo.hdqn_fresh_draws(fresh_words, k, opponent)
+            ubx, uby, ubz = mo.hdqn_fresh_draws(fresh_words, k, opponent)  # uniform: one call per step
             goal_t = g["goal"][t].astype(np.int64)
             x = np.concatenate([goal_t[:, None].astype(np.float32), obs], axis=1)  # [goal] + state
             q1 = mo.qnet_reference(lower_sd, x, bf16=True)
@@ -293,6 +296,9 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
                 exp_a2 = np.where(go, qa.argmax(1), _pick(uc[:, 1], 5))
                 cc_o.check(a2_all[t], exp_a2, go, qa, f"opponent action, launch {launch} step {t}",
                            q_exact=exact_q(op_lower_sd, xo))
+                a2 = a2_all[t].astype(np.int8)
+            elif opponent == "uniform":  # the action is the stream's word, no net and no excuse
+                np.testing.assert_array_equal(a2_all[t], _pick(ubz, 5), err_msg=f"launch {launch} step {t}")
                 a2 = a2_all[t].astype(np.int8)
             o_obs, o_rew, o_done, o_coll, _, o_fobs, err = coracle.step(envs, a1_all[t].astype(np.int8), a2,
                                                                         autoreset=True, final_obs=True, stats=stats,
