@@ -40,6 +40,11 @@
  *   mg_host_dqn_learn (ABI 21): DQN.learn (scripts/main.py:122-157; HDQN.learn hdqn.py:186-221,
  *                     Goal_DQN.learn hdqn.py:104-139) -- the minibatch update from the replay ring:
  *                     Double-DQN target, MSE, Adam, the target copy; fp32 in a documented order
+ *   mg_rainbow_pack / mg_rainbow_packed_bytes / mg_rainbow_forward / mg_host_rainbow_head: RainbowDQN's
+ *                     acting forward (scripts/ranbowdqn.py:517-548: noisy dueling C51 net, act()) -- bf16
+ *                     MFMA layers, the distributional head in fp32 in a documented order
+ *   mg_rollout_rainbow T steps of ranbowdqn.py's acting loop (:662-680: act on the state, act on the
+ *                     view rotated by three, env.step) in one launch
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -602,6 +607,76 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
                       uint64_t first_update, uint64_t seed, uint64_t first_draw, int32_t filled_only,
                       const mg_dqn_hyper* hyper, float* loss_out, float* rows_out, void* scratch,
                       size_t scratch_bytes);
+
+/* ---- Rainbow acting (additive to ABI 21) ------------------------------------------------------------
+ * The acting path of scripts/ranbowdqn.py: RainbowDQN.forward / act (:517-548) and the loop that calls
+ * them once per env step (:662-680). The net is exactly the reference's RainbowDQN(10, 5): Linear(10, 32),
+ * ReLU, Linear(32, 64), ReLU; value stream NoisyLinear(64, 64), ReLU, NoisyLinear(64, 51); advantage
+ * stream NoisyLinear(64, 64), ReLU, NoisyLinear(64, 5 * 51); support z = linspace(Vmin, Vmax, 51). The
+ * caller passes each layer's EFFECTIVE fp32 weight and bias (mu + sigma * epsilon of a noisy layer in
+ * training mode, :468-470, or mu), so between two reset_noise() calls the policy is a fixed function. Learning
+ * (compute_td_loss :584-609, projection_distribution :554-582) is not here.
+ *
+ * mg_rainbow_pack (replaces nothing of the reference: it prepares the weights): writes
+ * mg_rainbow_packed_bytes() = 74,192 bytes, 16-byte aligned -- bf16 weights (round to nearest even) as the
+ * forward's MFMA fragments in consumption order, the fp32 biases of layers 2..6, the fp32 support. Accepted:
+ * in_dim 10, hidden 32 / 64 / 64, 5 actions, 51 atoms; any other shape is refused.
+ *
+ * Arithmetic of the forward (mg_rainbow_forward, mg_rollout_rainbow), the contract the tests restate:
+ *   matrix layers  bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16, one chain of MFMAs per
+ *                  output over its k-blocks of 32 in ascending order. The input is x[j] = obs[(j + rotate)
+ *                  % 10] rounded to bf16. Layer 1 (K = 10): the chain starts at +0 and b1 is inside the K
+ *                  sum as three bf16 parts hi + mid + lo == b1 at k = 10, 11, 12 against inputs 1.0 (k = 13
+ *                  .. 31 are zero). Layers 2..6 (K = 32 or 64): the chain starts from the fp32 bias; within
+ *                  a k-block of 32 the hidden unit at k = 8 g + j is 32 kb + 16 (j >> 2) + 4 g + (j & 3).
+ *                  A hidden activation is the accumulator rounded to bf16 once, then max(., +0).
+ *   head, fp32     in this fixed order (no contraction; every operation rounded once), per env, with
+ *                  v[i] the value logits and A[a][i] the advantage logits:
+ *                    mean[i] = ((((A[0][i] + A[1][i]) + A[2][i]) + A[3][i]) + A[4][i]) / 5
+ *                    x[a][i] = (v[i] + A[a][i]) - mean[i]
+ *                    m[a]    = max_i x[a][i]
+ *                    e[a][i] = exp(x[a][i] - m[a])   (below)
+ *                    S[a], N[a]: the 51 atoms as FOUR chains over i = 13 g .. min(13 g + 12, 50), g = 0..3,
+ *                              each from +0 in ascending i -- S_g = S_g + e, N_g = N_g + e * z[i] (product
+ *                              rounded, then the sum) -- combined as (c0 + c1) + (c2 + c3)
+ *                    q[a]    = N[a] / S[a];   action = the lowest a with the largest q[a].
+ *                  (Four chains, not one over i = 0..50: the lane that holds an accumulator row owns its
+ *                  atom, and a column of the 16x16 tile is spread over four lanes.)
+ *   exp            the library's own, identical bits on host and device: 0 for x < -87 (and NaN); else
+ *                  k = rint(x * fp32(log2 e)), r = fmaf(k, 2.12194440e-4f, fmaf(k, -0.693359375f, x)),
+ *                  p = the degree-7 Taylor polynomial of exp(r) in Horner form, one fmaf per coefficient
+ *                  1/5040, 1/720, 1/120, 1/24, 1/6, 1/2, 1, 1, and the result p * 2^k (exact: normal).
+ *                  Never the hardware exponential.
+ *
+ * mg_rainbow_forward replaces RainbowDQN.forward up to the logits and act() (:543-548) for obs [n, 10]:
+ * optional outputs logits [n, 306] (value [51], then advantage [5][51]: the rows the head consumes), q [n, 5]
+ * fp32 and action [n] int8; a NULL output is not written. 0 <= rotate < 10; the opponent's view
+ * state[3:] + state[:3] (:669) is rotate = 3.
+ *
+ * mg_rollout_rainbow replaces :662-680 (act, act on the rotated view, env.step, reset at an episode end) for
+ * num_steps steps in one launch: mg_rollout_qnet's arguments without the Philox ones (there is no draw).
+ * opponent_mode 0: action_op = None, the env's own L0 opponent; 2: the same net on the rotated view.
+ * traj and stats as mg_rollout_random; mg_episode_stats.q_eval is left unchanged (the script logs none) and
+ * ret1_sum is ranbowdqn.py's episode_reward (:676).
+ *
+ * mg_host_rainbow_head: the head above on HOST memory, synchronously -- logits [n, 306] and support [51] to
+ * q [n, 5] and action [n] (either may be NULL) -- the same functions the kernels compile.
+ * mg_host_rainbow_exp: y[i] = that exp of x[i] on host memory, so its error can be measured (the head only
+ * ever passes x <= 0; x > 0 gives NaN here). */
+size_t mg_rainbow_packed_bytes(void);
+int mg_rainbow_pack(const float* linear1_w, const float* linear1_b, const float* linear2_w, const float* linear2_b,
+                    const float* value1_w, const float* value1_b, const float* value2_w, const float* value2_b,
+                    const float* advantage1_w, const float* advantage1_b, const float* advantage2_w,
+                    const float* advantage2_b, const float* support, int32_t in_dim, int32_t hidden1,
+                    int32_t hidden2, int32_t hidden_stream, int32_t num_actions, int32_t num_atoms, void* packed,
+                    void* stream);
+int mg_rainbow_forward(const void* packed, const float* obs, int32_t rotate, float* logits, float* q,
+                       int8_t* action, int64_t n, void* stream);
+int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                       int64_t n, int32_t num_steps, const void* net, int32_t opponent_mode, uint32_t flags,
+                       void* stream);
+int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n);
+int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
 
 #ifdef __cplusplus
 }

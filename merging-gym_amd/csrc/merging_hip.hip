@@ -32,8 +32,10 @@
 #include "mg_wave_out.h"        // a wave's outputs: LDS-staged observations, won mask, step bytes
 #include "mg_step.h"            // step_kernel, rollout_kernel
 #include "mg_qnet.h"            // the bf16 MFMA Q-net: pack kernels, forwards
+#include "mg_rainbow.h"         // Rainbow's acting net: pack kernel, MFMA forward, the fp32 head
 #include "mg_rollout_qnet.h"    // config 5: qnet_rollout_ws_kernel
 #include "mg_rollout_hdqn.h"    // the h-DQN acting loop: hdqn_rollout_kernel
+#include "mg_rollout_rainbow.h" // Rainbow's acting loop: rainbow_rollout_kernel
 #include "mg_reset_observe.h"   // reset_kernel, observe_kernel
 #include "mg_replay.h"          // the replay ring: scan, write and sample kernels
 #include "mg_launch.h"          // error text, armed events, argument checks, launch helpers
@@ -525,6 +527,96 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
                      rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
     host_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0);
   }
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- Rainbow acting (scripts/ranbowdqn.py:517-548, :662-680) ----------------------------------------
+size_t mg_rainbow_packed_bytes(void) { return static_cast<size_t>(kRbNetBytes); }
+
+int mg_rainbow_pack(const float* linear1_w, const float* linear1_b, const float* linear2_w, const float* linear2_b,
+                    const float* value1_w, const float* value1_b, const float* value2_w, const float* value2_b,
+                    const float* advantage1_w, const float* advantage1_b, const float* advantage2_w,
+                    const float* advantage2_b, const float* support, int32_t in_dim, int32_t hidden1,
+                    int32_t hidden2, int32_t hidden_stream, int32_t num_actions, int32_t num_atoms, void* packed,
+                    void* stream) {
+  const RbTensors T{linear1_w, linear1_b, linear2_w, linear2_b, value1_w, value1_b, value2_w,
+                    value2_b, advantage1_w, advantage1_b, advantage2_w, advantage2_b, support};
+  if (!T.w1 || !T.b1 || !T.w2 || !T.b2 || !T.wv1 || !T.bv1 || !T.wv2 || !T.bv2 || !T.wa1 || !T.ba1 || !T.wa2 ||
+      !T.ba2 || !T.z || !packed)
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_pack: NULL pointer");
+  if (in_dim != kRbIn || hidden1 != kRbH1 || hidden2 != kRbH2 || hidden_stream != kRbHS ||
+      num_actions != kRbActions || num_atoms != kRbAtoms)
+    return fail(hipErrorInvalidValue, "%s",
+                "mg_rainbow_pack: only RainbowDQN(10, 5) is packed: in_dim 10, hidden 32 / 64 / 64, 5 actions, 51 atoms");
+  if (misaligned(packed, 15))
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_pack: packed buffer must be 16-byte aligned");
+  for (const float* p : {T.w1, T.b1, T.w2, T.b2, T.wv1, T.bv1, T.wv2, T.bv2, T.wa1, T.ba1, T.wa2, T.ba2, T.z})
+    if (misaligned(p, 3)) return fail(hipErrorInvalidValue, "%s", "mg_rainbow_pack: the tensors must be 4-byte aligned");
+  hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(stream), T, static_cast<uint8_t*>(packed));
+  return finish_launch("mg_rainbow_pack");
+}
+
+int mg_rainbow_forward(const void* packed, const float* obs, int32_t rotate, float* logits, float* q,
+                       int8_t* action, int64_t n, void* stream) {
+  if (!obs) return fail(hipErrorInvalidValue, "%s", "mg_rainbow_forward: obs is NULL");
+  if (int e = check_packed_net(packed, "mg_rainbow_forward: packed must be a 16-byte aligned packed Rainbow net"))
+    return e;
+  if (rotate < 0 || rotate >= kObs) return fail(hipErrorInvalidValue, "%s", "mg_rainbow_forward: need 0 <= rotate < 10");
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (n > (static_cast<int64_t>(0x7fffffff) * kBlock)) return fail(hipErrorInvalidValue, "%s", "n exceeds the grid limit");
+  if (misaligned(obs, 3) || misaligned(logits, 3) || misaligned(q, 3))
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_forward: obs, logits and q must be 4-byte aligned");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rainbow_forward_kernel, dim3(grid_blocks(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const uint8_t*>(packed), obs, rotate, logits, q, action, n);
+  return finish_launch("mg_rainbow_forward");
+}
+
+int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                       int64_t n, int32_t num_steps, const void* net, int32_t opponent_mode, uint32_t flags,
+                       void* stream) {
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (int e = check_packed_net(net, "mg_rollout_rainbow: net must be a 16-byte aligned packed Rainbow net")) return e;
+  if (num_steps < 0 || num_steps > 65535)
+    return fail(hipErrorInvalidValue, "%s", "need 0 <= num_steps <= 65535 (split longer rollouts)");
+  if (opponent_mode != 0 && opponent_mode != 2)
+    return fail(hipErrorInvalidValue, "%s",
+                "mg_rollout_rainbow: opponent_mode must be 0 (None) or 2 (the same net on state[3:] + state[:3])");
+  if (int e = check_traj(traj)) return e;
+  if (n == 0 || num_steps == 0) return 0;
+  RbRollout R{};
+  R.P = *params;
+  R.R0 = reset0(*params);
+  R.S = *state;
+  R.T = *traj;
+  if (stats) R.St = *stats;
+  R.net = static_cast<const uint8_t*>(net);
+  R.n = n;
+  R.num_steps = num_steps;
+  R.flags = flags;
+  launch(opponent_mode == 0 ? rainbow_rollout_kernel<0> : rainbow_rollout_kernel<2>, grid_blocks(n, kRbThreads),
+         kRbThreads, static_cast<hipStream_t>(stream), R);
+  return finish_launch("mg_rollout_rainbow");
+}
+
+int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n) {
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (!logits || !support) return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_head: logits or support is NULL");
+  if (misaligned(logits, 3) || misaligned(support, 3) || misaligned(q, 3))
+    return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_head: logits, support and q must be 4-byte aligned");
+  for (int64_t i = 0; i < n; ++i)
+    host_rainbow_head_row(logits + i * kRbLogits, support, q ? q + i * kRbActions : nullptr, action ? action + i : nullptr);
+  g_err[0] = '\0';
+  return 0;
+}
+
+
+int mg_host_rainbow_exp(const float* x, float* y, int64_t n) {
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (!x || !y) return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_exp: NULL pointer");
+  for (int64_t i = 0; i < n; ++i) y[i] = x[i] > 0.0f ? NAN : rb_exp(x[i]);  // the head never passes x > 0
   g_err[0] = '\0';
   return 0;
 }

@@ -7,7 +7,7 @@ is importable. Without gym, `merging_gym.make(id)` builds the same envs.
 
 from .envs import MergeEnv, MergeEnvExtend, MergeVecEnv
 
-__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "DQNLearner", "make", "ENV_IDS"]
+__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "DQNLearner", "RainbowNet", "make", "ENV_IDS"]
 
 
 def __getattr__(name):  # ReplayRing and DQNLearner load the native library on first use only
@@ -19,6 +19,10 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .learn import DQNLearner
 
         return DQNLearner
+    if name == "RainbowNet":
+        from .rainbow import RainbowNet
+
+        return RainbowNet
     raise AttributeError(name)
 
 ENV_IDS = {

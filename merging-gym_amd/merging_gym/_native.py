@@ -173,6 +173,17 @@ def _load(path=LIB_PATH):
     lib.mg_host_dqn_learn.argtypes = learn_args + [_P, _c.c_size_t]
     for f in (lib.mg_dqn_learner_init, lib.mg_dqn_learn, lib.mg_host_dqn_learn):
         f.restype = _c.c_int
+    # Rainbow acting (additive to ABI 21): the packed net, its forward, the fused rollout, the host head
+    lib.mg_rainbow_packed_bytes.restype = _c.c_size_t
+    lib.mg_rainbow_pack.argtypes = [_P] * 13 + [_c.c_int32] * 6 + [_P, _P]
+    lib.mg_rainbow_forward.argtypes = [_P, _P, _c.c_int32, _P, _P, _P, _c.c_int64, _P]
+    lib.mg_rollout_rainbow.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _P, _c.c_int32,
+                                       _c.c_uint32, _P]
+    lib.mg_host_rainbow_head.argtypes = [_P, _P, _P, _P, _c.c_int64]
+    lib.mg_host_rainbow_exp.argtypes = [_P, _P, _c.c_int64]
+    for f in (lib.mg_rainbow_pack, lib.mg_rainbow_forward, lib.mg_rollout_rainbow, lib.mg_host_rainbow_head,
+              lib.mg_host_rainbow_exp):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

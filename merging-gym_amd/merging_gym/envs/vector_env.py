@@ -371,6 +371,23 @@ class MergeVecEnv:
         self._step_idx = k0 + T
         return buf["_result"]
 
+    def rollout_rainbow(self, num_steps: int, net, opponent: str = "self", final_observation: bool = True,
+                        won_mask: bool = True):
+        """`num_steps` steps of ranbowdqn.py's acting loop (:662-680) in one launch: action =
+        current_model.act(state) (:668) on the device (`net`, a RainbowNet: bf16 MFMA layers, the
+        distributional head in fp32), fused with the env step. opponent: "self" (:669, the same net on the
+        view state[3:] + state[:3]) or "none" (action_op = None, the env's own L0 opponent). There is no
+        draw: the exploration is in the net's noise buffers (RainbowNet.reset_noise). Returns the same
+        [T, N, ...] dict as rollout_qnet; the episode statistics' r1 sums are the script's episode_reward."""
+        nat = self._nat
+        T, n = int(num_steps), self.num_envs
+        mode = {"none": 0, "self": 2}[opponent]
+        buf = self._traj(T, final_observation, won_mask)
+        rc = nat.lib.mg_rollout_rainbow(self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, n, T,
+                                        net.packed.data_ptr(), mode, self._flags, self._stream())
+        nat.check(rc, "mg_rollout_rainbow")
+        return buf["_result"]
+
     def rollout_hdqn(self, num_steps: int, meta, lower, seed: int, opponent="none",
                      episilo: float = 0.7, first_step=None, final_observation: bool = True,
                      won_mask: bool = False, ring=None, goal_memory: bool = False):
