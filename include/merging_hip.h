@@ -45,6 +45,10 @@
  *                     MFMA layers, the distributional head in fp32 in a documented order
  *   mg_rollout_rainbow T steps of ranbowdqn.py's acting loop (:662-680: act on the state, act on the
  *                     view rotated by three, env.step) in one launch
+ *   mg_rainbow_replay_store / mg_rainbow_learn / mg_rainbow_learner_bytes / mg_rainbow_learn_scratch_bytes /
+ *   mg_host_rainbow_learn / mg_host_rainbow_project / mg_host_rainbow_log: ranbowdqn.py's ReplayBuffer.push
+ *                     (:281-288) and compute_td_loss (:554-609) -- C51 projection, noisy-net backward, Adam,
+ *                     the noise reset; fp32 in a documented order
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -615,7 +619,7 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
  * stream NoisyLinear(64, 64), ReLU, NoisyLinear(64, 5 * 51); support z = linspace(Vmin, Vmax, 51). The
  * caller passes each layer's EFFECTIVE fp32 weight and bias (mu + sigma * epsilon of a noisy layer in
  * training mode, :468-470, or mu), so between two reset_noise() calls the policy is a fixed function. Learning
- * (compute_td_loss :584-609, projection_distribution :554-582) is not here.
+ * (compute_td_loss :584-609, projection_distribution :554-582) is the next section's.
  *
  * mg_rainbow_pack (replaces nothing of the reference: it prepares the weights): writes
  * mg_rainbow_packed_bytes() = 74,192 bytes, 16-byte aligned -- bf16 weights (round to nearest even) as the
@@ -677,6 +681,86 @@ int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_
                        void* stream);
 int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n);
 int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
+
+/* ---- Rainbow learning (additive to ABI 21) ----------------------------------------------------------
+ * compute_td_loss (scripts/ranbowdqn.py:584-609) with projection_distribution (:554-582) on the device, and
+ * the (s, a, r, s', done) ReplayBuffer (:265-323) it samples from.
+ *
+ * mg_rainbow_replay_store replaces replay_buffer.push (:281-288, :673) for num_steps steps of n envs: rows
+ * [capacity, 24] fp32 = [s(10), a, r, s'(10), done, 0]. Transition (t, i) goes to slot (counter + t n + i) %
+ * capacity; s = obs_first[i] at t = 0, else obs[t - 1, i]; s' = final_obs[t, i] where done (and final_obs is
+ * given), else obs[t, i]; a and done from a1 / done or from flags; r = rew[t, i, 0]. Every transition is kept
+ * (no winner filter); when n num_steps > capacity only the newest `capacity` are written, so no two threads
+ * write one slot. One store launch, then counter += n num_steps on the same stream. mg_transitions' goal,
+ * next_goal, reward, meta_goal and won_mask have no meaning here (the first four must be NULL).
+ * mg_replay_sample(row_floats 24, filled_only 1) draws from these rows.
+ *
+ * The learner is one caller-owned device buffer of mg_rainbow_learner_bytes() = 4 (4 P + 2 E + 52) bytes,
+ * 16-byte aligned: current, target, Adam's exp_avg, Adam's exp_avg_sq -- P = 58,884 fp32 each in
+ * RainbowDQN.named_parameters() order: linear1.weight [32, 10], linear1.bias, linear2.weight [64, 32],
+ * linear2.bias, then per noisy layer (noisy_value1 [64, 64], noisy_value2 [51, 64], noisy_advantage1
+ * [64, 64], noisy_advantage2 [255, 64]) weight_mu, weight_sigma, bias_mu, bias_sigma -- then the current and the
+ * target model's noise, E = 28,210 fp32 each: per noisy layer weight_epsilon, bias_epsilon, the full buffers
+ * as the reference's state dict holds them -- then the support z[51] and one zero. The caller fills it (a
+ * target := current copy, noise included, is update_target, :551-552) and draws the noise factors.
+ *
+ * One update, fp32, in this fixed order -- the same for every grid, no float atomics; fmaf is the fused
+ * multiply-add, every other operation is rounded once:
+ *   minibatch   row b = the ring row at mg_replay_sample's slot (seed, draw = first_draw + u, filled_only 1).
+ *   effective   W = mu + sigma * eps (the product rounded, then the sum) of both models' noisy layers.
+ *   forwards    target(s') then current(s), both with their noise: per unit y = fmaf(x[K-1], W[j, K-1], ...
+ *               fmaf(x[0], W[j, 0], bias[j])), k ascending; ReLU keeps y > 0 ? y : 0. Per action the head of
+ *               the acting path: mean, x = (v + A) - mean, m = max, e = exp(x - m) (that exp), S = the four
+ *               13-atom chains combined (c0 + c1) + (c2 + c3), y[a][i] = e / S.
+ *   target      nd[a][i] = y[a][i] * z[i]; q[a] = the same four chains over nd[a]; a' = the first maximum;
+ *               the gathered row nd[a'] stays support-scaled (:560-563). Tz = r + ((1 - done) * fp32(gamma))
+ *               * z[i], clamped to [-10, 10]; b = (Tz - -10) / 0.4f; proj[j] = from +0, for i ascending where
+ *               floor(b_i) == j: + nd[i] * (ceil(b_i) - b_i); then for i ascending where ceil(b_i) == j:
+ *               + nd[i] * (b_i - floor(b_i)). Where floor == ceil both terms are zero (:579-580).
+ *   loss        a = the row's action (truncated, kept in 0..4); c_i = min(max(y[a][i], 0.01f), 0.99f);
+ *               loss_b = -(((0 + proj_0 log(c_0)) + proj_1 log(c_1)) + ...), log below;
+ *               loss = (((0 + loss_0) + loss_1) + ...) * fp32(1 / B).
+ *   dlogits     g_i = -(proj_i / c_i) * fp32(1 / B); dot = fmaf(g_50, y_50, ... fmaf(g_0, y_0, 0));
+ *               dx_i = y_i * (g_i - dot); value logits: dv_i = dx_i; advantage logits: t = dx_i / 5,
+ *               dA[a][i] = dx_i - t, every other action -t.
+ *   backward    per layer as mg_dqn_learn: dW[j, k] the fmaf chain over b of dy[b, j] x[b, k] from +0, db[j]
+ *               the sequential sum, dx[b, k] the fmaf chain over j of dy[b, j] W[j, k] from +0 masked by the
+ *               input's ReLU, with W the effective weights. linear2's output gradient is (the value stream's
+ *               chain + the advantage stream's chain), then the mask. g_mu = g_W, g_sigma = g_W * eps.
+ *   Adam        mg_dqn_learn's, step s = first_update + u + 1.
+ *   noise       afterwards both models' buffers are rebuilt from noise[u] = [2][1124] (current, target; per
+ *               noisy layer eps_in[64], eps_out[out], bias noise[out]): weight_epsilon[j, k] = eps_out[j] *
+ *               eps_in[k], bias_epsilon = the bias noise (:486-491, :606-607).
+ *   log         the library's own, identical bits on host and device: x = 2^k m, m in [sqrt(1/2), sqrt 2),
+ *               f = m - 1, s = f / (2 + f), z = s s, w = z z, R = z (L1 + w L3) + w (L2 + w L4), h = (0.5 f) f,
+ *               log = (((s (h + R) + k ln2_lo) - h) + f) + k ln2_hi (fdlibm's logf, no fmaf).
+ * Launches per update: the row kernel (one block per minibatch row), four backward launches (the two head
+ * layers, the two hidden streams with linear2's output gradient, linear2, linear1), Adam with the loss sum,
+ * the noise reset with the next effective weights; one launch before the first update forms the effective
+ * weights of the stored noise. Optional outputs: loss_out [U], rows_out [U, B, 24], proj_out [U, B, 51],
+ * grads_out [U, P]; packed_out (16-byte aligned, mg_rainbow_packed_bytes()): the current model's effective
+ * weights after the last update in mg_rainbow_pack's layout (num_updates 0: of the stored state). scratch:
+ * mg_rainbow_learn_scratch_bytes(batch) bytes, 16-byte aligned. hyper: mg_dqn_hyper (target_period is not
+ * read: the caller syncs the target by episode count, :690-691). Accepted: 1 <= batch <= 1024, 1 <= capacity
+ * <= 2^32, num_updates >= 0, 0 <= beta < 1.
+ * mg_host_rainbow_learn: the same functions on HOST pointers, synchronously. mg_host_rainbow_project: the
+ * projection alone, next_dist [n, 51] (support-scaled), reward [n], done [n], support [51] -> proj [n, 51].
+ * mg_host_rainbow_log: y[i] = that log of x[i] for normal positive x (NaN otherwise). */
+int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                            int32_t num_steps, void* stream);
+size_t mg_rainbow_learner_bytes(void);
+size_t mg_rainbow_learn_scratch_bytes(int32_t batch);
+int mg_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
+                     int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
+                     const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out, float* proj_out,
+                     float* grads_out, void* packed_out, void* scratch, size_t scratch_bytes, void* stream);
+int mg_host_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
+                          int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
+                          const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out,
+                          float* proj_out, float* grads_out, void* scratch, size_t scratch_bytes);
+int mg_host_rainbow_project(const float* next_dist, const float* reward, const float* done, const float* support,
+                            double gamma, float* proj, int64_t n);
+int mg_host_rainbow_log(const float* x, float* y, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@
 #include "mg_stats_reduce.h"    // the fixed-order statistics reduction, goal_status_kernel
 #include "mg_host_env.h"        // the CPU single-env path
 #include "mg_learn.h"           // DQN.learn: the minibatch update kernels and their host twin
+#include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
 
 extern "C" {
 
@@ -617,6 +618,128 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n) {
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (!x || !y) return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_exp: NULL pointer");
   for (int64_t i = 0; i < n; ++i) y[i] = x[i] > 0.0f ? NAN : rb_exp(x[i]);  // the head never passes x > 0
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- Rainbow learning (scripts/ranbowdqn.py:265-323, :551-609) --------------------------------------
+int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                            int32_t num_steps, void* stream) {
+  if (!rows || !counter || !tr) return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: NULL pointer");
+  if (capacity < 1 || capacity > (int64_t{1} << 32))
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: need 1 <= capacity <= 2^32");
+  if (n < 0 || num_steps < 0)
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: n < 0 or num_steps < 0");
+  if (tr->goal || tr->next_goal || tr->reward || tr->meta_goal)
+    return fail(hipErrorInvalidValue, "%s",
+                "mg_rainbow_replay_store: goal, next_goal, reward and meta_goal must be NULL (Rainbow rows have none)");
+  if (n == 0 || num_steps == 0) return 0;
+  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
+    return fail(hipErrorInvalidValue, "%s",
+                "mg_rainbow_replay_store: obs_first, obs, a1 (or flags) and rew are required");
+  if (misaligned(rows, 7) || misaligned(counter, 7) || misaligned(tr->obs_first, 3) || misaligned(tr->obs, 3) ||
+      misaligned(tr->final_obs, 3) || misaligned(tr->rew, 3))
+    return fail(hipErrorInvalidValue, "%s",
+                "mg_rainbow_replay_store: rows and counter must be 8-byte, the float buffers 4-byte aligned");
+  if (n > (static_cast<int64_t>(0x7fffffff) * kBlock) / num_steps)
+    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: n * num_steps exceeds the grid limit");
+  RlStore R{};
+  R.X = *tr;
+  R.n = n;
+  R.total = n * num_steps;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
+  hipLaunchKernelGGL(rl_counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+  return finish_launch("mg_rainbow_replay_store");
+}
+
+size_t mg_rainbow_learner_bytes(void) { return static_cast<size_t>(kRlLearner) * sizeof(float); }
+
+size_t mg_rainbow_learn_scratch_bytes(int32_t batch) {
+  if (batch < 1 || batch > 1024) return 0;
+  return static_cast<size_t>(rl_scratch(batch).total) * sizeof(float);
+}
+
+int mg_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
+                     int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
+                     const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out, float* proj_out,
+                     float* grads_out, void* packed_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int e = check_rainbow_learn("mg_rainbow_learn", learner, rows, counter, capacity, batch, num_updates, hyper, noise,
+                                  loss_out, rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes))
+    return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
+  const unsigned eff_blocks = grid_blocks(2 * kRlEps);
+  // the effective weights of the stored noise; every update's last launch leaves the next one's
+  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(eff_blocks), dim3(kBlock), 0, st, L, 0);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
+                             noise, loss_out, rows_out, proj_out, grads_out);
+    hipLaunchKernelGGL(rl_forward_kernel, dim3(batch), dim3(2 * kRlThreads), 0, st, L);
+    const LearnBwd G0 = rl_bwd_layer(L, 0), G1 = rl_bwd_layer(L, 1), G2 = rl_bwd_layer(L, 2), G3 = rl_bwd_layer(L, 3);
+    hipLaunchKernelGGL(rl_bwd_heads_kernel, dim3(grid_blocks(learn_bwd_items(G0) + learn_bwd_items(G1))), dim3(kBlock),
+                       0, st, G0, G1);
+    hipLaunchKernelGGL(rl_bwd_streams_kernel, dim3(grid_blocks(rl_bwd_streams_items(L, G2, G3))), dim3(kBlock), 0, st, L,
+                       G2, G3);
+    for (int which = 4; which < 6; ++which) {
+      const LearnBwd G = rl_bwd_layer(L, which);
+      hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
+    }
+    hipLaunchKernelGGL(rl_adam_kernel, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
+    hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(eff_blocks), dim3(kBlock), 0, st, L, 1);
+  }
+  if (packed_out) {  // the acting kernels' layout of the current model's effective weights, on the same stream
+    const float* e = L.eff;
+    const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
+    const RbTensors T{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
+                      e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
+                      e + A1.e, e + A1.e + A1.out * kRbHS, e + A2.e, e + A2.e + A2.out * kRbHS, learner + kRlOffZ};
+    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st, T,
+                       static_cast<uint8_t*>(packed_out));
+  }
+  return finish_launch("mg_rainbow_learn");
+}
+
+int mg_host_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
+                          int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
+                          const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out,
+                          float* proj_out, float* grads_out, void* scratch, size_t scratch_bytes) {
+  if (int e = check_rainbow_learn("mg_host_rainbow_learn", learner, rows, counter, capacity, batch, num_updates, hyper,
+                                  noise, loss_out, rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes))
+    return e;
+  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
+  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
+                             noise, loss_out, rows_out, proj_out, grads_out);
+    host_rainbow_learn_update(L);
+  }
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_host_rainbow_project(const float* next_dist, const float* reward, const float* done, const float* support,
+                            double gamma, float* proj, int64_t n) {
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (!next_dist || !reward || !done || !support || !proj)
+    return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_project: NULL pointer");
+  if (misaligned(next_dist, 3) || misaligned(reward, 3) || misaligned(done, 3) || misaligned(support, 3) ||
+      misaligned(proj, 3))
+    return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_project: the arrays must be 4-byte aligned");
+  const float g = static_cast<float>(gamma);
+  for (int64_t r = 0; r < n; ++r) {
+    float bb[kRbAtoms];
+    for (int i = 0; i < kRbAtoms; ++i) bb[i] = rl_b(reward[r], done[r], g, support[i]);
+    for (int j = 0; j < kRbAtoms; ++j) proj[r * kRbAtoms + j] = rl_proj_slot(j, next_dist + r * kRbAtoms, bb);
+  }
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_host_rainbow_log(const float* x, float* y, int64_t n) {
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (!x || !y) return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_log: NULL pointer");
+  for (int64_t i = 0; i < n; ++i) y[i] = x[i] >= 1.17549435e-38f && x[i] < INFINITY ? rb_log(x[i]) : NAN;
   g_err[0] = '\0';
   return 0;
 }

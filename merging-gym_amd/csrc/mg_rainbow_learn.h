@@ -1,0 +1,542 @@
+// mg_rainbow_learn.h -- Rainbow's compute_td_loss on the device: the done-carrying replay store, the C51
+// projection, the noisy-net forward and backward, Adam and the noise reset, with the per-element functions
+// the host twin (mg_host_rainbow_learn) runs too.
+// A part of the one translation unit merging_hip.hip (see its head comment).
+#pragma once
+
+#include "mg_common.h"
+#include "mg_env.h"
+#include "mg_launch.h"
+#include "mg_learn.h"
+#include "mg_rainbow.h"
+
+namespace {
+
+// ============================================================================ Rainbow's replay rows
+// ReplayBuffer (scripts/ranbowdqn.py:265-323) as a ring of 24-float rows [s(10), a, r, s'(10), done, 0]:
+// push (:281-288) keeps every transition, so slot (counter + t n + i) % capacity needs no scan.
+constexpr int kRlRow = 24;
+constexpr int kRlColA = kObs, kRlColR = kObs + 1, kRlColS2 = kObs + 2, kRlColDone = 2 * kObs + 2;
+
+struct RlStore {
+  mg_transitions X;
+  int64_t n;
+  int64_t total;  // T n
+};
+
+__global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const uint64_t* counter, float* rows,
+                                                          int64_t cap) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  // only the newest `cap` transitions survive sequential pushes: they occupy distinct slots
+  const int64_t skip = R.total > cap ? R.total - cap : 0;
+  if (idx >= R.total || idx < skip) return;
+  const int64_t i = idx % R.n;
+  const bool done = R.X.flags ? R.X.flags[4 * idx + 2] != 0 : (R.X.done != nullptr && R.X.done[idx] != 0);
+  const float* s = idx < R.n ? R.X.obs_first + i * kObs : R.X.obs + (idx - R.n) * kObs;
+  const float* s2 = (done && R.X.final_obs ? R.X.final_obs : R.X.obs) + idx * kObs;
+  float v[kRlRow];
+#pragma unroll
+  for (int k = 0; k < kObs; ++k) v[k] = s[k], v[kRlColS2 + k] = s2[k];
+  v[kRlColA] = static_cast<float>(R.X.flags ? static_cast<int8_t>(R.X.flags[4 * idx]) : R.X.a1[idx]);
+  v[kRlColR] = R.X.rew[2 * idx];
+  v[kRlColDone] = done ? 1.0f : 0.0f;
+  v[kRlRow - 1] = 0.0f;
+  const uint64_t slot = (*counter + static_cast<uint64_t>(idx)) % static_cast<uint64_t>(cap);
+  f32x2* d = reinterpret_cast<f32x2*>(rows + slot * kRlRow);
+#pragma unroll
+  for (int k = 0; k < kRlRow / 2; ++k) d[k] = f32x2{v[2 * k], v[2 * k + 1]};
+}
+
+// after every thread of the store has read the old counter: the same stream orders it
+__global__ void rl_counter_add_kernel(uint64_t* counter, uint64_t k) { *counter += k; }
+
+// ============================================================================ compute_td_loss
+// scripts/ranbowdqn.py:554-609 on RainbowDQN(10, 5) with 51 atoms, all fp32 in the fixed order
+// include/merging_hip.h documents at mg_rainbow_learn. The learner buffer: current, target, Adam m, Adam v
+// (kRlParams each, RainbowDQN.named_parameters() order), the two models' full noise buffers (kRlEps each,
+// per noisy layer weight_epsilon then bias_epsilon), the support z[52].
+constexpr int kRlW1 = 0, kRlB1 = kRbH1 * kRbIn, kRlW2 = kRlB1 + kRbH1, kRlB2 = kRlW2 + kRbH2 * kRbH1;
+constexpr int kRlPlain = kRlB2 + kRbH2;  // 2,464
+constexpr int kRlParams = 58884, kRlEps = 28210, kRlFactors = 1124, kRlZ = 52;
+constexpr int kRlOffM = 2 * kRlParams, kRlOffV = 3 * kRlParams, kRlOffEps = 4 * kRlParams;
+constexpr int kRlOffZ = kRlOffEps + 2 * kRlEps, kRlLearner = kRlOffZ + kRlZ;
+constexpr int kRlThreads = 320;  // one thread per head unit (306)
+static_assert(kRlLearner % 4 == 0 && kRlThreads >= kRbLogits, "16-byte learner, a thread per logit");
+
+// Noisy layer l (0 value1, 1 value2, 2 advantage1, 3 advantage2; reset_noise's order, :537-541): its width,
+// the offset p of weight_mu in a parameter block (then weight_sigma, bias_mu, bias_sigma), the offset e of
+// weight_epsilon in a noise block (then bias_epsilon; the effective weights use the same layout) and the
+// offset f of its factors eps_in, eps_out, bias noise in one model's kRlFactors.
+struct RlNoisy {
+  int out, p, e, f;
+};
+MG_HD RlNoisy rl_noisy(int l) {
+  switch (l) {
+    case 0: return {kRbHS, kRlPlain, 0, 0};
+    case 1: return {kRbAtoms, kRlPlain + 8320, 4160, 192};
+    case 2: return {kRbHS, kRlPlain + 14950, 7475, 358};
+    default: return {kRbActions * kRbAtoms, kRlPlain + 23270, 11635, 550};
+  }
+}
+// the noisy layer that holds index i of a block whose layer l starts at start(l)
+MG_HD int rl_layer_of_eps(int e) { return e < 4160 ? 0 : e < 7475 ? 1 : e < 11635 ? 2 : 3; }
+MG_HD int rl_layer_of_param(int i) { return i < kRlPlain + 8320 ? 0 : i < kRlPlain + 14950 ? 1 : i < kRlPlain + 23270 ? 2 : 3; }
+
+struct RlScratch {  // sections (floats), each a multiple of four
+  int64_t rows, h1, h2, hv, ha, dlog, dhv, dha, dh2, dh1, lossb, g, geff, eff, total;
+};
+MG_HD RlScratch rl_scratch(int64_t B) {
+  RlScratch S;
+  S.rows = 0;
+  S.h1 = S.rows + B * kRlRow;
+  S.h2 = S.h1 + B * kRbH1;
+  S.hv = S.h2 + B * kRbH2;
+  S.ha = S.hv + B * kRbHS;
+  S.dlog = S.ha + B * kRbHS;
+  S.dhv = S.dlog + learn_round4(B * kRbLogits);
+  S.dha = S.dhv + B * kRbHS;
+  S.dh2 = S.dha + B * kRbHS;
+  S.dh1 = S.dh2 + B * kRbH2;
+  S.lossb = S.dh1 + B * kRbH1;
+  S.g = S.lossb + learn_round4(B);
+  S.geff = S.g + kRlPlain;
+  S.eff = S.geff + learn_round4(kRlEps);
+  S.total = S.eff + learn_round4(2 * kRlEps);
+  return S;
+}
+
+// Everything one update's launches (or the host loops) read.
+struct RLearn {
+  float* buf;  // the learner buffer
+  const float* ring;
+  const uint64_t* counter;
+  int64_t cap;
+  uint64_t seed, draw;
+  int32_t B;
+  float *rows, *h1, *h2, *hv, *ha, *dlog, *dhv, *dha, *dh2, *dh1, *lossb, *g, *geff, *eff;  // scratch sections
+  const float* noise;  // this update's factors [2][kRlFactors]: current, target
+  float *rows_out, *loss_out, *proj_out, *grads_out;  // this update's, or NULL
+  float gamma, inv_b;
+  LearnAdam A;
+};
+
+// ---------------------------------------------------------------------------- per-element functions
+// log(x) for a normal x > 0, the same bits on host and device (the loss takes it on [0.01, 0.99]): x = 2^k m
+// with m in [sqrt(1/2), sqrt 2), f = m - 1, s = f / (2 + f), log(1 + f) = f - f^2/2 + s (f^2/2 + R(s^2)) with
+// the classic degree-4 minimax R in s^2 (fdlibm's logf), and k ln 2 added in two parts. Every operation is
+// rounded once; no fmaf. Not the hardware v_log_f32, which the host cannot reproduce.
+MG_HD float rb_log(float x) {
+  uint32_t ix = __builtin_bit_cast(uint32_t, x);
+  ix += 0x3f800000u - 0x3f3504f3u;
+  const float dk = static_cast<float>(static_cast<int>(ix >> 23) - 127);
+  ix = (ix & 0x007fffffu) + 0x3f3504f3u;
+  const float f = __builtin_bit_cast(float, ix) - 1.0f;
+  const float s = f / (2.0f + f);
+  const float z = s * s;
+  const float w = z * z;
+  const float t1 = w * (0.40000972152f + w * 0.24279078841f);
+  const float t2 = z * (0.66666662693f + w * 0.28498786688f);
+  const float R = t2 + t1;
+  const float hfsq = (0.5f * f) * f;
+  return (((s * (hfsq + R) + dk * 9.0580006145e-06f) - hfsq) + f) + dk * 6.9313812256e-01f;
+}
+
+// the 51 atoms as four chains over 13 g .. 13 g + 12, each from +0 ascending, combined (c0 + c1) + (c2 + c3)
+// (host_rainbow_head_row's order)
+MG_HD float rl_sum4(const float* v) {
+  float c[4];
+  for (int g = 0; g < 4; ++g) {
+    c[g] = 0.0f;
+    for (int i = kRbSlots * g; i < kRbSlots * (g + 1) && i < kRbAtoms; ++i) c[g] = c[g] + v[i];
+  }
+  return (c[0] + c[1]) + (c[2] + c[3]);
+}
+
+// element t = 51 a + i of the dueling combination from the logits lg [306] (value [51], advantage [5][51])
+MG_HD float rl_head_x(const float* lg, int t) {
+  const float* A = lg + kRbAtoms;
+  const int i = t % kRbAtoms;
+  const float mean = rb_mean(A[i], A[kRbAtoms + i], A[2 * kRbAtoms + i], A[3 * kRbAtoms + i], A[4 * kRbAtoms + i]);
+  return rb_duel(lg[i], A[t], mean);
+}
+MG_HD float rl_max51(const float* x) {
+  float m = -INFINITY;
+  for (int i = 0; i < kRbAtoms; ++i) m = fmaxf(m, x[i]);
+  return m;
+}
+// softmax over the atoms of action a into p [51], in the head's order: x, m = max, e = exp(x - m), S the four
+// chains, e / S (the kernel runs the same steps with one thread per element)
+MG_HD void rl_softmax(const float* lg, int a, float* p) {
+  for (int i = 0; i < kRbAtoms; ++i) p[i] = rl_head_x(lg, a * kRbAtoms + i);
+  const float m = rl_max51(p);
+  for (int i = 0; i < kRbAtoms; ++i) p[i] = rb_exp(p[i] - m);
+  const float S = rl_sum4(p);
+  for (int i = 0; i < kRbAtoms; ++i) p[i] = p[i] / S;
+}
+
+// b of atom z (:569-571): Tz = r + ((1 - done) gamma) z clamped to the support, (Tz - Vmin) / delta_z
+MG_HD float rl_b(float r, float done, float gamma, float z) {
+  float tz = r + ((1.0f - done) * gamma) * z;
+  tz = fminf(fmaxf(tz, -10.0f), 10.0f);
+  return (tz - -10.0f) / 0.4f;
+}
+
+// slot j of proj_dist (:578-580): every l contribution in atom order, then every u contribution, each a
+// rounded product added into the slot from +0; nd is the support-scaled row of the chosen action
+MG_HD float rl_proj_slot(int j, const float* nd, const float* bb) {
+  const float fj = static_cast<float>(j);
+  float acc = 0.0f;
+  for (int i = 0; i < kRbAtoms; ++i)
+    if (floorf(bb[i]) == fj) acc = acc + nd[i] * (ceilf(bb[i]) - bb[i]);
+  for (int i = 0; i < kRbAtoms; ++i)
+    if (ceilf(bb[i]) == fj) acc = acc + nd[i] * (bb[i] - floorf(bb[i]));
+  return acc;
+}
+
+// loss_b = -sum_i proj_i log(c_i), c = clamp(y, 0.01, 0.99) (:598-599), the products summed from +0 in atom
+// order; dx [51] = the gradient at the chosen action's logits: g_i = -(proj_i / c_i) (1 / B) (log's backward
+// sees the clamped copy), dot = the fmaf chain of g_k y_k from +0, dx_i = y_i (g_i - dot) (softmax's backward
+// sees y)
+MG_HD float rl_loss_row(const float* y, const float* proj, float inv_b, float* dx) {
+  float acc = 0.0f, dot = 0.0f;
+  for (int i = 0; i < kRbAtoms; ++i) {
+    const float c = fminf(fmaxf(y[i], 0.01f), 0.99f);
+    acc = acc + proj[i] * rb_log(c);
+    dx[i] = -(proj[i] / c) * inv_b;
+    dot = fmaf(dx[i], y[i], dot);
+  }
+  for (int i = 0; i < kRbAtoms; ++i) dx[i] = y[i] * (dx[i] - dot);
+  return -acc;
+}
+
+// the gradient at logit t of [306] through the dueling combination: dv_i = dx_i, dA[a][i] = dx_i (d(a, a*) - 1/5)
+MG_HD float rl_dlogit(const float* dx, int astar, int t) {
+  if (t < kRbAtoms) return dx[t];
+  const int a = (t - kRbAtoms) / kRbAtoms, i = (t - kRbAtoms) - a * kRbAtoms;
+  const float fifth = dx[i] / 5.0f;
+  return a == astar ? dx[i] - fifth : -fifth;
+}
+
+// one unit of each layer: P a parameter block, eff that model's effective noisy weights
+MG_HD float rl_unit_h1(const float* P, const float* x, int j) {
+  return learn_relu(learn_fwd(x, P + kRlW1 + j * kRbIn, P[kRlB1 + j], kRbIn));
+}
+MG_HD float rl_unit_h2(const float* P, const float* h1, int j) {
+  return learn_relu(learn_fwd(h1, P + kRlW2 + j * kRbH1, P[kRlB2 + j], kRbH1));
+}
+MG_HD float rl_unit_noisy(const float* eff, int l, const float* x, int j) {
+  const RlNoisy N = rl_noisy(l);
+  return learn_fwd(x, eff + N.e + j * kRbHS, eff[N.e + N.out * kRbHS + j], kRbHS);
+}
+MG_HD float rl_unit_logit(const float* eff, const float* hv, const float* ha, int t) {
+  return t < kRbAtoms ? rl_unit_noisy(eff, 1, hv, t) : rl_unit_noisy(eff, 3, ha, t - kRbAtoms);
+}
+
+// the first maximum of q [5]
+MG_HD int rl_argmax(const float* q) {
+  int best = 0;
+  for (int a = 1; a < kRbActions; ++a)
+    if (q[a] > q[best]) best = a;
+  return best;
+}
+
+// Element idx of (model, e) over the two noise blocks: with factors, the new epsilon (eps_out[j] eps_in[k],
+// one rounded product as ger gives; the bias noise as drawn) is stored first; then the effective value
+// mu + sigma * eps (the product rounded, then the sum) of that model.
+MG_HD void rl_noise_eff_at(const RLearn& L, int idx, bool redraw) {
+  const int model = idx / kRlEps, e = idx - model * kRlEps;
+  const RlNoisy N = rl_noisy(rl_layer_of_eps(e));
+  const int r = e - N.e, nw = N.out * kRbHS;
+  float* eps = L.buf + kRlOffEps + model * kRlEps + e;
+  if (redraw) {
+    const float* F = L.noise + model * kRlFactors + N.f;
+    *eps = r < nw ? F[kRbHS + r / kRbHS] * F[r % kRbHS] : F[kRbHS + N.out + (r - nw)];
+  }
+  const float* P = L.buf + model * kRlParams + N.p;
+  const float mu = r < nw ? P[r] : P[2 * nw + (r - nw)];
+  const float sigma = r < nw ? P[nw + r] : P[2 * nw + N.out + (r - nw)];
+  L.eff[model * kRlEps + e] = mu + sigma * *eps;
+}
+
+// the gradient of parameter i: the plain layers' as computed; a noisy layer's g_mu = g_w, g_sigma = g_w eps
+MG_HD float rl_param_grad(const RLearn& L, int i) {
+  if (i < kRlPlain) return L.g[i];
+  const RlNoisy N = rl_noisy(rl_layer_of_param(i));
+  const int nw = N.out * kRbHS;
+  int r = i - N.p;
+  const float* eps = L.buf + kRlOffEps;  // the current model's
+  if (r < nw) return L.geff[N.e + r];
+  if (r < 2 * nw) return L.geff[N.e + r - nw] * eps[N.e + r - nw];
+  r -= 2 * nw;
+  if (r < N.out) return L.geff[N.e + nw + r];
+  return L.geff[N.e + nw + r - N.out] * eps[N.e + nw + r - N.out];
+}
+
+// item i of the Adam launch: parameter i, or at i == kRlParams the loss, the sequential sum of loss_b times 1 / B
+MG_HD void rl_adam_at(const RLearn& L, int i) {
+  if (i == kRlParams) {
+    if (L.loss_out) *L.loss_out = learn_sum(L.lossb, 1, L.B) * L.inv_b;
+    return;
+  }
+  const float g = rl_param_grad(L, i);
+  if (L.grads_out) L.grads_out[i] = g;
+  learn_adam(L.buf[i], L.buf[kRlOffM + i], L.buf[kRlOffV + i], g, L.A);
+}
+
+// the hidden streams' input gradient: dh2[b, k] = the value stream's chain plus the advantage stream's, then
+// the mask of linear2's ReLU
+MG_HD void rl_dh2_at(const RLearn& L, int64_t idx) {
+  const int64_t b = idx / kRbH2;
+  const int k = static_cast<int>(idx - b * kRbH2);
+  const float v = learn_chain(L.dhv + b * kRbHS, 1, L.eff + rl_noisy(0).e + k, kRbH2, kRbHS);
+  const float a = learn_chain(L.dha + b * kRbHS, 1, L.eff + rl_noisy(2).e + k, kRbH2, kRbHS);
+  const float s = v + a;
+  L.dh2[idx] = L.h2[idx] > 0.0f ? s : 0.0f;
+}
+
+// The backward launches' layers: 0 value2, 1 advantage2 (with the hidden streams' dx), 2 value1, 3 advantage1
+// (gradients only: rl_dh2_at sums their dx), 4 linear2, 5 linear1.
+MG_HD LearnBwd rl_bwd_layer(const RLearn& L, int which) {
+  LearnBwd G{};
+  G.B = L.B;
+  G.inv_b = L.inv_b;
+  if (which < 4) {
+    static_assert(kRbH2 == kRbHS, "the streams' inputs are all 64 wide");
+    const int l = which == 0 ? 1 : which == 1 ? 3 : which == 2 ? 0 : 2;
+    const RlNoisy N = rl_noisy(l);
+    G.nJ = N.out, G.nK = kRbHS, G.sx = kRbHS;
+    G.W = L.eff + N.e, G.gW = L.geff + N.e, G.gb = L.geff + N.e + N.out * kRbHS;
+    if (which == 0) G.dy = L.dlog, G.sdy = kRbLogits, G.x = L.hv, G.dx = L.dhv;
+    if (which == 1) G.dy = L.dlog + kRbAtoms, G.sdy = kRbLogits, G.x = L.ha, G.dx = L.dha;
+    if (which == 2) G.dy = L.dhv, G.sdy = kRbHS, G.x = L.h2;
+    if (which == 3) G.dy = L.dha, G.sdy = kRbHS, G.x = L.h2;
+  } else if (which == 4) {
+    G.dy = L.dh2, G.sdy = kRbH2, G.nJ = kRbH2;
+    G.x = L.h1, G.sx = kRbH1, G.nK = kRbH1;
+    G.W = L.buf + kRlW2, G.gW = L.g + kRlW2, G.gb = L.g + kRlB2;
+    G.dx = L.dh1;
+  } else {
+    G.dy = L.dh1, G.sdy = kRbH1, G.nJ = kRbH1;
+    G.x = L.rows, G.sx = kRlRow, G.nK = kRbIn;
+    G.W = L.buf + kRlW1, G.gW = L.g + kRlW1, G.gb = L.g + kRlB1;
+  }
+  return G;
+}
+
+// Row b's part of an update on plain memory -- both forwards, the projection, loss_b and dlogits -- which the
+// host twin runs as it stands; rl_forward_kernel gives the same steps one thread per unit.
+inline void host_rl_forward_row(const RLearn& L, uint64_t live, int b) {
+  const float* row = L.ring + learn_slot(static_cast<uint64_t>(b), L.draw, L.seed, live) * kRlRow;
+  const float* z = L.buf + kRlOffZ;
+  float h1[kRbH1], h2[kRbH2], hv[kRbHS], ha[kRbHS], lg[kRbLogits], p[kRbActions * kRbAtoms], q[kRbActions];
+  float bb[kRbAtoms], proj[kRbAtoms], dx[kRbAtoms];
+  for (int k = 0; k < kRlRow; ++k) {
+    L.rows[b * kRlRow + k] = row[k];
+    if (L.rows_out) L.rows_out[b * kRlRow + k] = row[k];
+  }
+  for (int pass = 1; pass >= 0; --pass) {  // target(s'), then current(s)
+    const float* P = L.buf + pass * kRlParams;
+    const float* eff = L.eff + pass * kRlEps;
+    const float* x = row + (pass ? kRlColS2 : 0);
+    for (int j = 0; j < kRbH1; ++j) h1[j] = rl_unit_h1(P, x, j);
+    for (int j = 0; j < kRbH2; ++j) h2[j] = rl_unit_h2(P, h1, j);
+    for (int j = 0; j < kRbHS; ++j) hv[j] = learn_relu(rl_unit_noisy(eff, 0, h2, j));
+    for (int j = 0; j < kRbHS; ++j) ha[j] = learn_relu(rl_unit_noisy(eff, 2, h2, j));
+    for (int t = 0; t < kRbLogits; ++t) lg[t] = rl_unit_logit(eff, hv, ha, t);
+    for (int a = 0; a < kRbActions; ++a) rl_softmax(lg, a, p + a * kRbAtoms);
+    if (pass) {
+      for (int a = 0; a < kRbActions; ++a) {
+        for (int i = 0; i < kRbAtoms; ++i) p[a * kRbAtoms + i] = p[a * kRbAtoms + i] * z[i];
+        q[a] = rl_sum4(p + a * kRbAtoms);
+      }
+      const float* nd = p + rl_argmax(q) * kRbAtoms;
+      for (int i = 0; i < kRbAtoms; ++i) bb[i] = rl_b(row[kRlColR], row[kRlColDone], L.gamma, z[i]);
+      for (int j = 0; j < kRbAtoms; ++j) {
+        proj[j] = rl_proj_slot(j, nd, bb);
+        if (L.proj_out) L.proj_out[b * kRbAtoms + j] = proj[j];
+      }
+    } else {
+      const int astar = learn_action(row[kRlColA], kRbActions);
+      L.lossb[b] = rl_loss_row(p + astar * kRbAtoms, proj, L.inv_b, dx);
+      for (int t = 0; t < kRbLogits; ++t) L.dlog[b * kRbLogits + t] = rl_dlogit(dx, astar, t);
+      for (int j = 0; j < kRbH1; ++j) L.h1[b * kRbH1 + j] = h1[j];
+      for (int j = 0; j < kRbH2; ++j) L.h2[b * kRbH2 + j] = h2[j];
+      for (int j = 0; j < kRbHS; ++j) L.hv[b * kRbHS + j] = hv[j], L.ha[b * kRbHS + j] = ha[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------- kernels
+// One block per minibatch row: host_rl_forward_row's steps, the activations in LDS, one thread per unit. The two
+// forwards run side by side -- threads 0..319 the target's on s' (pass 1), 320..639 the current's on s (pass 0) --
+// through the same phases; only the loss waits for the projection.
+__global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const RLearn L) {
+  __shared__ float srow[kRlRow], h1[2][kRbH1], h2[2][kRbH2], hv[2][kRbHS], ha[2][kRbHS], lg[2][kRbLogits];
+  __shared__ float p[2][kRbActions * kRbAtoms], q[2][kRbActions], bb[kRbAtoms], proj[kRbAtoms], dx[kRbAtoms];
+  const int b = blockIdx.x;
+  const int pass = threadIdx.x < kRlThreads ? 1 : 0, t = threadIdx.x - (pass ? 0 : kRlThreads);
+  const float* z = L.buf + kRlOffZ;
+  if (threadIdx.x < kRlRow) {
+    const uint64_t live = learn_rows_live(L.cap, L.counter, 1);
+    const float v = L.ring[learn_slot(static_cast<uint64_t>(b), L.draw, L.seed, live) * kRlRow + threadIdx.x];
+    srow[threadIdx.x] = v;
+    L.rows[b * kRlRow + threadIdx.x] = v;
+    if (L.rows_out) L.rows_out[b * kRlRow + threadIdx.x] = v;
+  }
+  __syncthreads();
+  const float* P = L.buf + pass * kRlParams;
+  const float* eff = L.eff + pass * kRlEps;
+  const float* x = srow + (pass ? kRlColS2 : 0);
+  if (t < kRbH1) h1[pass][t] = rl_unit_h1(P, x, t);
+  __syncthreads();
+  if (t < kRbH2) h2[pass][t] = rl_unit_h2(P, h1[pass], t);
+  __syncthreads();
+  if (t < kRbHS)
+    hv[pass][t] = learn_relu(rl_unit_noisy(eff, 0, h2[pass], t));
+  else if (t < 2 * kRbHS)
+    ha[pass][t - kRbHS] = learn_relu(rl_unit_noisy(eff, 2, h2[pass], t - kRbHS));
+  __syncthreads();
+  if (t < kRbLogits) lg[pass][t] = rl_unit_logit(eff, hv[pass], ha[pass], t);
+  __syncthreads();
+  // rl_softmax's steps, one thread per (action, atom), the two reductions one thread per action
+  const int ha5 = t / kRbAtoms;  // the action of element t < 255
+  if (t < kRbActions * kRbAtoms) p[pass][t] = rl_head_x(lg[pass], t);
+  if (pass && t >= 256 && t < 256 + kRbAtoms)  // another wave than the reductions'
+    bb[t - 256] = rl_b(srow[kRlColR], srow[kRlColDone], L.gamma, z[t - 256]);
+  __syncthreads();
+  if (t < kRbActions) q[pass][t] = rl_max51(p[pass] + t * kRbAtoms);
+  __syncthreads();
+  if (t < kRbActions * kRbAtoms) p[pass][t] = rb_exp(p[pass][t] - q[pass][ha5]);
+  __syncthreads();
+  if (t < kRbActions) q[pass][t] = rl_sum4(p[pass] + t * kRbAtoms);
+  __syncthreads();
+  if (t < kRbActions * kRbAtoms) {
+    const float y = p[pass][t] / q[pass][ha5];
+    p[pass][t] = pass ? y * z[t - ha5 * kRbAtoms] : y;
+  }
+  __syncthreads();
+  if (pass && t < kRbActions) q[1][t] = rl_sum4(p[1] + t * kRbAtoms);
+  if (!pass) {  // the current model's activations, for the backward launches
+    if (t < kRbH1) L.h1[b * kRbH1 + t] = h1[0][t];
+    if (t >= 64 && t < 64 + kRbH2) L.h2[b * kRbH2 + t - 64] = h2[0][t - 64];
+    if (t >= 128 && t < 128 + kRbHS) L.hv[b * kRbHS + t - 128] = hv[0][t - 128];
+    if (t >= 192 && t < 192 + kRbHS) L.ha[b * kRbHS + t - 192] = ha[0][t - 192];
+  }
+  __syncthreads();
+  if (pass && t < kRbAtoms) {
+    proj[t] = rl_proj_slot(t, p[1] + rl_argmax(q[1]) * kRbAtoms, bb);
+    if (L.proj_out) L.proj_out[b * kRbAtoms + t] = proj[t];
+  }
+  __syncthreads();
+  const int astar = learn_action(srow[kRlColA], kRbActions);
+  if (!pass && t == 0) L.lossb[b] = rl_loss_row(p[0] + astar * kRbAtoms, proj, L.inv_b, dx);
+  __syncthreads();
+  if (!pass && t < kRbLogits) L.dlog[b * kRbLogits + t] = rl_dlogit(dx, astar, t);
+}
+
+// two layers' items in one launch
+__global__ __launch_bounds__(kBlock) void rl_bwd_heads_kernel(const LearnBwd G0, const LearnBwd G1) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int64_t n0 = learn_bwd_items(G0);
+  if (idx < n0)
+    learn_bwd_at(G0, idx);
+  else if (idx < n0 + learn_bwd_items(G1))
+    learn_bwd_at(G1, idx - n0);
+}
+
+// the hidden streams' gradients and, behind them, the B x 64 items of rl_dh2_at
+__global__ __launch_bounds__(kBlock) void rl_bwd_streams_kernel(const RLearn L, const LearnBwd Gv, const LearnBwd Ga) {
+  int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int64_t nv = learn_bwd_items(Gv), na = learn_bwd_items(Ga);
+  if (idx < nv) return learn_bwd_at(Gv, idx);
+  idx -= nv;
+  if (idx < na) return learn_bwd_at(Ga, idx);
+  idx -= na;
+  if (idx < static_cast<int64_t>(L.B) * kRbH2) rl_dh2_at(L, idx);
+}
+MG_HD int64_t rl_bwd_streams_items(const RLearn& L, const LearnBwd& Gv, const LearnBwd& Ga) {
+  return learn_bwd_items(Gv) + learn_bwd_items(Ga) + static_cast<int64_t>(L.B) * kRbH2;
+}
+
+__global__ __launch_bounds__(kBlock) void rl_adam_kernel(const RLearn L) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i <= kRlParams) rl_adam_at(L, i);
+}
+
+__global__ __launch_bounds__(kBlock) void rl_noise_eff_kernel(const RLearn L, int redraw) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < 2 * kRlEps) rl_noise_eff_at(L, i, redraw != 0);
+}
+
+// ---------------------------------------------------------------------------- host side of a call
+// What mg_rainbow_learn and mg_host_rainbow_learn refuse, before anything is read or launched.
+int check_rainbow_learn(const char* what, const float* learner, const float* rows, const uint64_t* counter,
+                        int64_t capacity, int32_t batch, int32_t num_updates, const mg_dqn_hyper* hyper,
+                        const float* noise, const float* loss_out, const float* rows_out, const float* proj_out,
+                        const float* grads_out, const void* packed_out, const void* scratch, size_t scratch_bytes) {
+  if (!learner || !rows || !counter || !hyper || !scratch) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (batch < 1 || batch > 1024) return fail(hipErrorInvalidValue, "%s: need 1 <= batch <= 1024", what);
+  if (capacity < 1 || capacity > (int64_t{1} << 32))
+    return fail(hipErrorInvalidValue, "%s: need 1 <= capacity <= 2^32", what);
+  if (num_updates < 0) return fail(hipErrorInvalidValue, "%s: num_updates < 0", what);
+  if (num_updates > 0 && !noise)
+    return fail(hipErrorInvalidValue, "%s: noise is NULL (num_updates x 2 x 1124 factors)", what);
+  if (!(hyper->beta1 >= 0.0 && hyper->beta1 < 1.0 && hyper->beta2 >= 0.0 && hyper->beta2 < 1.0))
+    return fail(hipErrorInvalidValue, "%s: need 0 <= beta1 < 1 and 0 <= beta2 < 1", what);
+  if (misaligned(learner, 15) || misaligned(scratch, 15) || misaligned(packed_out, 15) || misaligned(rows, 7) ||
+      misaligned(counter, 7) || misaligned(noise, 3) || misaligned(loss_out, 3) || misaligned(rows_out, 3) ||
+      misaligned(proj_out, 3) || misaligned(grads_out, 3))
+    return fail(hipErrorInvalidValue,
+                "%s: learner, scratch and packed_out must be 16-byte, rows and counter 8-byte, noise and the "
+                "optional outputs 4-byte aligned", what);
+  if (scratch_bytes < static_cast<size_t>(rl_scratch(batch).total) * sizeof(float))
+    return fail(hipErrorInvalidValue, "%s: scratch smaller than mg_rainbow_learn_scratch_bytes(batch)", what);
+  return 0;
+}
+
+// The fields of RLearn that do not change from one update of a call to the next.
+RLearn make_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
+                          uint64_t seed, const mg_dqn_hyper* hyper, void* scratch) {
+  const RlScratch S = rl_scratch(batch);
+  float* s = static_cast<float*>(scratch);
+  RLearn L{};
+  L.buf = learner;
+  L.ring = rows, L.counter = counter, L.cap = capacity, L.seed = seed, L.B = batch;
+  L.rows = s + S.rows, L.h1 = s + S.h1, L.h2 = s + S.h2, L.hv = s + S.hv, L.ha = s + S.ha, L.dlog = s + S.dlog;
+  L.dhv = s + S.dhv, L.dha = s + S.dha, L.dh2 = s + S.dh2, L.dh1 = s + S.dh1, L.lossb = s + S.lossb;
+  L.g = s + S.g, L.geff = s + S.geff, L.eff = s + S.eff;
+  L.gamma = static_cast<float>(hyper->gamma);
+  L.inv_b = static_cast<float>(1.0 / batch);
+  return L;
+}
+
+// Update number u of a call: its draw, factors, optional outputs and (through a Learn, whose Adam scalars
+// learn_set_update computes) Adam's step first_update + u + 1.
+void rainbow_learn_set_update(RLearn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw, int32_t u, const float* noise,
+                              float* loss_out, float* rows_out, float* proj_out, float* grads_out) {
+  Learn tmp{};
+  learn_set_update(tmp, h, t, draw, nullptr, nullptr);
+  L.A = tmp.A;
+  L.draw = draw;
+  L.noise = noise + static_cast<int64_t>(u) * 2 * kRlFactors;
+  L.loss_out = loss_out ? loss_out + u : nullptr;
+  L.rows_out = rows_out ? rows_out + static_cast<int64_t>(u) * L.B * kRlRow : nullptr;
+  L.proj_out = proj_out ? proj_out + static_cast<int64_t>(u) * L.B * kRbAtoms : nullptr;
+  L.grads_out = grads_out ? grads_out + static_cast<int64_t>(u) * kRlParams : nullptr;
+}
+
+// One update on the host (mg_host_rainbow_learn): the kernels' per-item functions in the kernels' order.
+void host_rainbow_learn_update(const RLearn& L) {
+  const uint64_t live = learn_rows_live(L.cap, L.counter, 1);
+  for (int b = 0; b < L.B; ++b) host_rl_forward_row(L, live, b);
+  for (int which = 0; which < 6; ++which) {
+    const LearnBwd G = rl_bwd_layer(L, which);
+    for (int64_t i = 0; i < learn_bwd_items(G); ++i) learn_bwd_at(G, i);
+    if (which == 3)
+      for (int64_t i = 0; i < static_cast<int64_t>(L.B) * kRbH2; ++i) rl_dh2_at(L, i);
+  }
+  for (int i = 0; i <= kRlParams; ++i) rl_adam_at(L, i);
+  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, true);
+}
+
+}  // namespace

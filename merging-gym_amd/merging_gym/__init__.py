@@ -7,7 +7,8 @@ is importable. Without gym, `merging_gym.make(id)` builds the same envs.
 
 from .envs import MergeEnv, MergeEnvExtend, MergeVecEnv
 
-__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "DQNLearner", "RainbowNet", "make", "ENV_IDS"]
+__all__ = ["MergeEnv", "MergeEnvExtend", "MergeVecEnv", "ReplayRing", "DQNLearner", "RainbowNet", "RainbowReplay",
+           "RainbowLearner", "make", "ENV_IDS"]
 
 
 def __getattr__(name):  # ReplayRing and DQNLearner load the native library on first use only
@@ -23,6 +24,10 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .rainbow import RainbowNet
 
         return RainbowNet
+    if name in ("RainbowReplay", "RainbowLearner"):
+        from . import rainbow_learn
+
+        return getattr(rainbow_learn, name)
     raise AttributeError(name)
 
 ENV_IDS = {

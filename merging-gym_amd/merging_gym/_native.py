@@ -184,6 +184,20 @@ def _load(path=LIB_PATH):
     for f in (lib.mg_rainbow_pack, lib.mg_rainbow_forward, lib.mg_rollout_rainbow, lib.mg_host_rainbow_head,
               lib.mg_host_rainbow_exp):
         f.restype = _c.c_int
+    # Rainbow learning (additive to ABI 21): the done-carrying replay store, compute_td_loss, its host twin
+    lib.mg_rainbow_replay_store.argtypes = [_P, _P, _c.c_int64, _c.POINTER(Transitions), _c.c_int64, _c.c_int32, _P]
+    lib.mg_rainbow_learner_bytes.restype = _c.c_size_t
+    lib.mg_rainbow_learn_scratch_bytes.argtypes = [_c.c_int32]
+    lib.mg_rainbow_learn_scratch_bytes.restype = _c.c_size_t
+    rl_args = [_P, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64,
+               _c.POINTER(DqnHyper), _P, _P, _P, _P, _P]
+    lib.mg_rainbow_learn.argtypes = rl_args + [_P, _P, _c.c_size_t, _P]
+    lib.mg_host_rainbow_learn.argtypes = rl_args + [_P, _c.c_size_t]
+    lib.mg_host_rainbow_project.argtypes = [_P, _P, _P, _P, _c.c_double, _P, _c.c_int64]
+    lib.mg_host_rainbow_log.argtypes = [_P, _P, _c.c_int64]
+    for f in (lib.mg_rainbow_replay_store, lib.mg_rainbow_learn, lib.mg_host_rainbow_learn,
+              lib.mg_host_rainbow_project, lib.mg_host_rainbow_log):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

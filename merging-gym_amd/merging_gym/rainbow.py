@@ -8,7 +8,7 @@ dueling C51 net -- as its act() evaluates it, packed for the fused bf16 MFMA ker
 
 The noisy layers act through their effective weights mu + sigma * epsilon (:468-470); the reference never
 calls .eval() and redraws epsilon only inside compute_td_loss, so between two learns the policy is a fixed
-function of those weights. Learning itself is not part of this module.
+function of those weights. Learning (compute_td_loss) is merging_gym.rainbow_learn's RainbowLearner.
 """
 
 from __future__ import annotations

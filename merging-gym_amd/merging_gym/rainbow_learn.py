@@ -1,0 +1,360 @@
+"""RainbowReplay and RainbowLearner: the reference's Rainbow training step on the device.
+
+Device twins of ReplayBuffer (scripts/ranbowdqn.py:265-323, the buffer main() builds at :647) and of
+compute_td_loss (:584-609) with projection_distribution (:554-582): a minibatch from the replay rows, the C51
+projection of the target net's distribution, the cross-entropy against the current net's, Adam(lr 0.001), and
+a fresh draw of both nets' noise. One call enqueues any number of updates on the current stream (seven kernel
+launches each, libmerging_hip.so's mg_rainbow_learn) and repacks the current net for the acting kernels, so
+the loop of ranbowdqn.py:662-691 closes without leaving the device:
+
+    replay = RainbowReplay(10000, device="cuda:0")
+    learner = RainbowLearner(RainbowNet.from_state_dict(sd, device="cuda:0"), replay)
+    obs0 = env.observe().clone()
+    traj = env.rollout_rainbow(16, learner.net)            # act + act on the rotated view + env.step
+    replay.store_rollout(obs0, traj)                       # replay_buffer.push, every transition
+    learner.learn(4)                                       # compute_td_loss, four times
+    traj = env.rollout_rainbow(16, learner.net)            # acts with the new weights and the new noise
+    learner.sync_target()                                  # update_target, every 20 episodes (:690-691)
+
+The arithmetic is fp32 in the fixed order include/merging_hip.h documents, so a run is reproducible bit for
+bit, also across a state_dict() / load_state_dict() resume. The noise is torch's: every update consumes the
+draws of two RainbowNet.reset_noise calls (the current model's, then the target's) from `generator`.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+from .rainbow import NOISY, NUM_ATOMS, PLAIN, SHAPES, RainbowNet
+
+ROW = 24  # [s(10), a, r, s'(10), done, 0]: 8-byte aligned rows mg_replay_sample copies as they are
+_OBS = 10
+
+# RainbowDQN.named_parameters() order, and the noise buffers per noisy layer
+PARAM_KEYS = tuple(f"{n}.{leaf}" for n in PLAIN for leaf in ("weight", "bias")) + tuple(
+    f"{n}.{leaf}" for n in NOISY for leaf in ("weight_mu", "weight_sigma", "bias_mu", "bias_sigma"))
+EPS_KEYS = tuple(f"{n}.{leaf}" for n in NOISY for leaf in ("weight_epsilon", "bias_epsilon"))
+
+
+def _shape(key):
+    name, leaf = key.split(".")
+    return SHAPES[name] if leaf.startswith("weight") else SHAPES[name][:1]
+
+
+def _numel(key):
+    s = _shape(key)
+    return s[0] * (s[1] if len(s) == 2 else 1)
+
+
+NUM_PARAMS = sum(_numel(k) for k in PARAM_KEYS)      # 58,884
+NUM_EPS = sum(_numel(k) for k in EPS_KEYS)           # 28,210
+NUM_FACTORS = sum(SHAPES[n][1] + 2 * SHAPES[n][0] for n in NOISY)  # 1,124 per model and update
+OFF_M, OFF_V, OFF_EPS = 2 * NUM_PARAMS, 3 * NUM_PARAMS, 4 * NUM_PARAMS
+OFF_Z = OFF_EPS + 2 * NUM_EPS
+LEARNER_FLOATS = OFF_Z + NUM_ATOMS + 1
+
+
+def learner_array(current, target=None):
+    """The learner buffer (a flat fp32 CPU tensor) from RainbowDQN state dicts: current, target (default: a
+    copy of current, noise included -- update_target, :551-552), zero Adam moments, both noise blocks, the
+    support."""
+    import torch
+
+    target = current if target is None else target
+    flat = lambda sd, keys: torch.cat([  # noqa: E731
+        torch.as_tensor(sd[k]).detach().to("cpu", torch.float32).reshape(-1) for k in keys])
+    buf = torch.cat([flat(current, PARAM_KEYS), flat(target, PARAM_KEYS), torch.zeros(2 * NUM_PARAMS),
+                     flat(current, EPS_KEYS), flat(target, EPS_KEYS), torch.linspace(-10, 10, NUM_ATOMS),
+                     torch.zeros(1)])
+    assert buf.numel() == LEARNER_FLOATS
+    return buf.contiguous()
+
+
+def model_state_dict(buf, model):
+    """RainbowDQN.state_dict() of model 0 (current) or 1 (target) of a learner buffer: copies, the reference's
+    keys, the epsilon buffers included."""
+    out = {}
+    at = model * NUM_PARAMS
+    for k in PARAM_KEYS:
+        out[k] = buf[at:at + _numel(k)].reshape(_shape(k)).clone()
+        at += _numel(k)
+    at = OFF_EPS + model * NUM_EPS
+    for k in EPS_KEYS:
+        out[k] = buf[at:at + _numel(k)].reshape(_shape(k)).clone()
+        at += _numel(k)
+    order = [f"{n}.{leaf}" for n in PLAIN for leaf in ("weight", "bias")] + [
+        f"{n}.{leaf}" for n in NOISY
+        for leaf in ("weight_mu", "weight_sigma", "bias_mu", "bias_sigma", "weight_epsilon", "bias_epsilon")]
+    return {k: out[k] for k in order}
+
+
+def noise_factors(num_updates, generator=None):
+    """[num_updates, 2, 1124] fp32: per update the factors of current_model.reset_noise() then
+    target_model.reset_noise() (:606-607) -- per noisy layer epsilon_in, epsilon_out, the bias noise (:486-491) --
+    the same stream as that many RainbowNet.reset_noise(generator) calls."""
+    import torch
+
+    out = torch.empty((int(num_updates), 2, NUM_FACTORS), dtype=torch.float32)
+    flat, at = out.view(-1), 0
+    sizes = [size for name in NOISY for size in (SHAPES[name][1], SHAPES[name][0], SHAPES[name][0])]
+    for _ in range(2 * int(num_updates)):  # one randn per draw, as _scale_noise makes them: the same stream
+        for size in sizes:
+            torch.randn(size, generator=generator, out=flat[at:at + size])
+            at += size
+    return out.sign().mul_(out.abs().sqrt_())  # _scale_noise's x.sign().mul(x.abs().sqrt()), elementwise
+
+
+class RainbowReplay:
+    """ReplayBuffer(capacity) (:265-323) as a ring of [capacity, 24] fp32 rows on the device; the position is
+    a device counter, so stores are stream-ordered and len() synchronises."""
+
+    def __init__(self, capacity: int = 10000, device=None):
+        import torch
+
+        from . import _native
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("RainbowReplay needs a ROCm GPU; there is no CPU fallback")
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self._torch, self._nat = torch, _native
+        self.capacity = int(capacity)
+        self.row = ROW
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.memory = torch.zeros((self.capacity, ROW), dtype=torch.float32, device=self.device)
+        self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def __len__(self):
+        """len(replay_buffer) (:278-279). Synchronises the stream."""
+        return min(int(self._counter.item()), self.capacity)
+
+    def _f32(self, t, shape):
+        torch = self._torch
+        t = torch.as_tensor(t, device=self.device)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(torch.float32).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def store(self, obs_first, obs, a1, rew, done=None, final_obs=None, flags=None):
+        """Append T steps of N envs ([T, N, ...] tensors; obs_first [N, 10] = the observation before step 0) in
+        (step, env) order, as pushing env 0..N-1 of each step in turn would. flags: a rollout's interleaved
+        [T, N, 4] buffer, read in place of a1 / done. One launch; nothing is synchronised."""
+        torch = self._torch
+        if flags is not None:
+            flags = torch.as_tensor(flags, device=self.device)
+            if flags.dtype != torch.uint8 or flags.dim() != 3 or flags.shape[2] != 4 or not flags.is_contiguous():
+                raise ValueError("flags must be a contiguous [T, N, 4] uint8 tensor")
+            T, n = flags.shape[:2]
+            a1, done = None, None
+        else:
+            a1 = torch.as_tensor(a1, device=self.device).to(torch.int8).contiguous()
+            T, n = a1.shape
+            if done is not None:
+                done = torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
+                if tuple(done.shape) != (T, n):
+                    raise ValueError(f"done must have shape {(T, n)}")
+        obs_first = self._f32(obs_first, (n, _OBS))
+        obs = self._f32(obs, (T, n, _OBS))
+        rew = self._f32(rew, (T, n, 2))
+        if final_obs is not None:
+            final_obs = self._f32(final_obs, (T, n, _OBS))
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        tr = self._nat.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), ptr(a1), ptr(rew), ptr(done), None,
+                                   None, None, None, ptr(flags), None)
+        rc = self._nat.lib.mg_rainbow_replay_store(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity,
+                                                   ctypes.byref(tr), n, T, self._stream())
+        self._nat.check(rc, "mg_rainbow_replay_store")
+        self._keepalive = (obs_first, obs, a1, rew, done, final_obs, flags)
+
+    def store_rollout(self, obs_first, traj):
+        """Append a MergeVecEnv rollout (the dict rollout_rainbow returns): every transition (:673). With
+        autoreset the obs row of a finished env is already the reset observation, so the terminal one comes
+        from final_observation."""
+        if traj.get("final_observation") is None:
+            raise ValueError("the rollout has no final_observation: episode ends would store the reset "
+                             "observation as next_state; roll out with final_observation=True")
+        self.store(obs_first, traj["obs"], traj["a1"], traj["rew"], traj["done"], traj["final_observation"],
+                   traj.get("flags"))
+
+    def push(self, state, action, reward, next_state, done):
+        """replay_buffer.push (:281-288), the reference's single call, through the same kernel."""
+        torch = self._torch
+        s = torch.as_tensor([list(map(float, state))], dtype=torch.float32)
+        s2 = torch.as_tensor([[list(map(float, next_state))]], dtype=torch.float32)
+        a = torch.as_tensor([[int(action)]], dtype=torch.int8)
+        r = torch.as_tensor([[[float(reward), 0.0]]], dtype=torch.float32)
+        d = torch.as_tensor([[1 if done else 0]], dtype=torch.uint8)
+        self.store(s.to(self.device), s2.to(self.device), a.to(self.device), r.to(self.device), d.to(self.device))
+
+    def sample_rows(self, batch_size: int = 32, seed: int = 0, draw: int = 0):
+        """[B, 24] rows at mg_replay_sample's Philox slots among the rows stored so far (the reference draws
+        from len(storage), :322)."""
+        torch = self._torch
+        rows = torch.empty((int(batch_size), ROW), dtype=torch.float32, device=self.device)
+        rc = self._nat.lib.mg_replay_sample(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity, ROW,
+                                            seed & 0xFFFFFFFFFFFFFFFF, draw & 0xFFFFFFFFFFFFFFFF, 1, rows.data_ptr(),
+                                            None, int(batch_size), self._stream())
+        self._nat.check(rc, "mg_replay_sample")
+        return rows
+
+    def sample(self, batch_size: int = 32, seed: int = 0, draw: int = 0):
+        """(state [B, 10], action [B] int64, reward [B], next_state [B, 10], done [B]) -- ReplayBuffer.sample's
+        five arrays (:302-323)."""
+        rows = self.sample_rows(batch_size, seed, draw)
+        return (rows[:, :_OBS], rows[:, _OBS].to(self._torch.int64), rows[:, _OBS + 1],
+                rows[:, _OBS + 2:2 * _OBS + 2], rows[:, 2 * _OBS + 2])
+
+    def state_dict(self):
+        return {"memory": self.memory.clone(), "counter": self._counter.clone()}
+
+    def load_state_dict(self, sd):
+        mem = self._torch.as_tensor(sd["memory"])
+        if tuple(mem.shape) != tuple(self.memory.shape):
+            raise ValueError(f"expected a {tuple(self.memory.shape)} replay memory")
+        self.memory.copy_(mem)
+        self._counter.copy_(self._torch.as_tensor(sd["counter"]))
+
+
+class _LearnerNet(RainbowNet):
+    """The RainbowNet a learner owns: `packed` is the buffer mg_rainbow_learn rewrites, and the host-side
+    `state` is read back from the learner's device buffer whenever a learn, a sync or a load has changed it."""
+
+    _learner = None
+    _stale = False
+
+    @property
+    def state(self):
+        if self._stale and self._learner is not None:
+            self._stale = False
+            for k, v in self._learner.current_state_dict().items():
+                self._state[k].copy_(v)
+        return self._state
+
+    @state.setter
+    def state(self, value):
+        self._state = value
+
+    @property
+    def packed(self):
+        return self._learner._packed
+
+    def reset_noise(self, generator=None):
+        raise RuntimeError("the learner owns this net's noise: RainbowLearner.learn() redraws it")
+
+
+class RainbowLearner:
+    def __init__(self, net, replay, lr: float = 0.001, gamma: float = 0.99, batch_size: int = 32, seed: int = 0,
+                 generator=None, device=None, betas=(0.9, 0.999), eps: float = 1e-8):
+        """net: a RainbowNet, or a RainbowDQN.state_dict(); the current and the target model both start from
+        it, noise included (update_target, :648). replay: the RainbowReplay learn() draws from. lr, gamma,
+        batch_size: ranbowdqn.py:645, :569, :652. seed: the key of the minibatch draws (update u draws what
+        replay.sample(batch_size, seed, draw=u) returns). generator: the torch.Generator of the noise draws
+        (None: torch's global one, as the reference)."""
+        import torch
+
+        from . import _native
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("RainbowLearner needs a ROCm GPU; there is no CPU fallback")
+        self._torch, self._nat = torch, _native
+        self.replay = replay
+        self.device = torch.device(device) if device is not None else replay.device
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self.device != replay.device:
+            raise ValueError(f"the replay memory lives on {replay.device}, the learner on {self.device}")
+        sd = net.state if isinstance(net, RainbowNet) else net
+        self.batch_size = int(batch_size)
+        self.hyper = _native.DqnHyper(float(lr), float(gamma), float(betas[0]), float(betas[1]), float(eps), 1, 0)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.generator = generator
+        self.learn_step_counter = 0  # Adam's step count
+        self.draw_counter = 0        # minibatches drawn so far
+        assert int(_native.lib.mg_rainbow_learner_bytes()) == 4 * LEARNER_FLOATS
+        self._buf = learner_array(sd).to(self.device)
+        sbytes = int(_native.lib.mg_rainbow_learn_scratch_bytes(self.batch_size))
+        if sbytes == 0:
+            raise ValueError("batch_size must be in 1..1024")
+        self._scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=self.device)
+        self._scratch_bytes = sbytes
+        self._packed = torch.empty(int(_native.lib.mg_rainbow_packed_bytes()), dtype=torch.uint8, device=self.device)
+        self.net = _LearnerNet(model_state_dict(self._buf, 0), training=True, device=self.device)
+        self.net._learner = self
+        self._call(0)
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None):
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = self._nat.lib.mg_rainbow_learn(
+            self._buf.data_ptr(), self.replay.memory.data_ptr(), self.replay._counter.data_ptr(),
+            self.replay.capacity, self.batch_size, U, self.learn_step_counter, self.seed, self.draw_counter,
+            ctypes.byref(self.hyper), ptr(noise), ptr(loss), ptr(rows), ptr(proj), ptr(grads),
+            self._packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes, self._stream())
+        self._nat.check(rc, "mg_rainbow_learn")
+        self.net._stale = True
+
+    def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
+              return_proj: bool = False, return_grads: bool = False):
+        """num_updates times compute_td_loss (:584-609), enqueued back to back on the current stream, then the
+        acting net repacked; nothing is synchronised. Returns None, the one requested device tensor, or a
+        tuple of the requested ones in the order loss [U], rows [U, B, 24], proj [U, B, 51], grads [U, P]
+        (the gradients in named_parameters() order)."""
+        torch = self._torch
+        U = int(num_updates)
+        if U < 0:
+            raise ValueError("num_updates must be >= 0")
+        B = self.batch_size
+        new = lambda want, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if want else None  # noqa: E731
+        loss, rows = new(return_loss, U), new(return_rows, U, B, ROW)
+        proj, grads = new(return_proj, U, B, NUM_ATOMS), new(return_grads, U, NUM_PARAMS)
+        if U > 0:
+            noise = noise_factors(U, self.generator).to(self.device)
+            self._call(U, noise, loss, rows, proj, grads)
+            self._keepalive = noise
+            self.learn_step_counter += U
+            self.draw_counter += U
+        out = tuple(t for t in (loss, rows, proj, grads) if t is not None)
+        return None if not out else out[0] if len(out) == 1 else out
+
+    def sync_target(self):
+        """update_target (:551-552, :690-691): target := current, noise included."""
+        b = self._buf
+        b[NUM_PARAMS:2 * NUM_PARAMS].copy_(b[:NUM_PARAMS])
+        b[OFF_EPS + NUM_EPS:OFF_EPS + 2 * NUM_EPS].copy_(b[OFF_EPS:OFF_EPS + NUM_EPS])
+
+    def current_state_dict(self):
+        """current_model.state_dict() as ranbowdqn.py:699 saves it (copies, torch-loadable)."""
+        return model_state_dict(self._buf, 0)
+
+    def target_state_dict(self):
+        return model_state_dict(self._buf, 1)
+
+    def state_dict(self):
+        """Both models with their noise, Adam's moments, the counters and the noise generator's state: a run
+        resumed from it continues bit for bit."""
+        return {"learner": self._buf.clone(), "learn_step_counter": self.learn_step_counter,
+                "draw_counter": self.draw_counter, "seed": self.seed,
+                "generator": None if self.generator is None else self.generator.get_state()}
+
+    def load_state_dict(self, sd):
+        buf = self._torch.as_tensor(sd["learner"])
+        if buf.numel() != self._buf.numel():
+            raise ValueError("expected the state of a RainbowLearner")
+        self._buf.copy_(buf.to(self._torch.float32).reshape(-1))
+        self.learn_step_counter = int(sd["learn_step_counter"])
+        self.draw_counter = int(sd["draw_counter"])
+        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        if sd.get("generator") is not None:
+            if self.generator is None:
+                self.generator = self._torch.Generator()
+            self.generator.set_state(sd["generator"])
+        self._call(0)

@@ -1,0 +1,199 @@
+"""Time of one Rainbow update (compute_td_loss) on the device (not part of bench.py).
+
+    python tools/rainbow_learn_bench.py [--out profiles/rainbow_learn_bench.json] [--updates 200] [--warmup 20]
+
+Per batch size (32, the reference's, and 128) in one process on one GPU:
+  ours_us        microseconds per update of RainbowLearner.learn(updates): HIP events around one call that draws
+                 the noise factors on the host, uploads them once and enqueues every update, after `warmup`
+                 untimed updates;
+  torch_us       ranbowdqn.py's compute_td_loss (:554-609) in eager torch on device tensors -- both forwards,
+                 the projection with index_add_, the clamped cross-entropy, Adam, both reset_noise calls (drawn
+                 on the host as the reference draws them) -- fed by RainbowReplay.sample, timed the same way;
+  launches       kernel launches per update and per_launch_us = ours_us / launches;
+  kernels        per kernel, the mean device time of one launch and the launches per update, from
+                 torch.profiler's kernel records of a separate pass of 20 updates. null if the profiler gave
+                 no kernel records.
+Best of `repeats` alternating runs. The replay memory holds seeded random rows and the nets their default
+initialisation: the time does not depend on the values.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "merging-gym_amd"))
+
+BATCHES = (32, 128)
+LAUNCHES = 7  # rows + both forwards + projection + dlogits, four backward launches, Adam + loss, noise + effective
+
+
+def torch_rainbow(torch, dev):
+    """RainbowDQN(10, 5) and compute_td_loss in eager torch on `dev`."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    atoms, vmin, vmax = 51, -10.0, 10.0
+
+    class Noisy(nn.Module):
+        def __init__(self, i, o):
+            super().__init__()
+            self.i, self.o = i, o
+            r = 1 / math.sqrt(i)
+            self.weight_mu = nn.Parameter(torch.empty(o, i).uniform_(-r, r))
+            self.weight_sigma = nn.Parameter(torch.full((o, i), 0.4 / math.sqrt(i)))
+            self.bias_mu = nn.Parameter(torch.empty(o).uniform_(-r, r))
+            self.bias_sigma = nn.Parameter(torch.full((o,), 0.4 / math.sqrt(o)))
+            self.register_buffer("weight_epsilon", torch.zeros(o, i))
+            self.register_buffer("bias_epsilon", torch.zeros(o))
+            self.reset_noise()
+
+        @staticmethod
+        def scale(n):
+            x = torch.randn(n)
+            return x.sign().mul(x.abs().sqrt())
+
+        def reset_noise(self):
+            self.weight_epsilon.copy_(self.scale(self.o).ger(self.scale(self.i)))
+            self.bias_epsilon.copy_(self.scale(self.o))
+
+        def forward(self, x):
+            return F.linear(x, self.weight_mu + self.weight_sigma * self.weight_epsilon,
+                            self.bias_mu + self.bias_sigma * self.bias_epsilon)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.linear1, self.linear2 = nn.Linear(10, 32), nn.Linear(32, 64)
+            self.noisy_value1, self.noisy_value2 = Noisy(64, 64), Noisy(64, atoms)
+            self.noisy_advantage1, self.noisy_advantage2 = Noisy(64, 64), Noisy(64, 5 * atoms)
+
+        def forward(self, x):
+            x = F.relu(self.linear2(F.relu(self.linear1(x))))
+            v = self.noisy_value2(F.relu(self.noisy_value1(x))).view(-1, 1, atoms)
+            a = self.noisy_advantage2(F.relu(self.noisy_advantage1(x))).view(-1, 5, atoms)
+            return F.softmax(v + a - a.mean(1, keepdim=True), dim=2)
+
+        def reset_noise(self):
+            for m in (self.noisy_value1, self.noisy_value2, self.noisy_advantage1, self.noisy_advantage2):
+                m.reset_noise()
+
+    current, target = Net().to(dev), Net().to(dev)
+    target.load_state_dict(current.state_dict())
+    opt = torch.optim.Adam(current.parameters(), 0.001)
+    support = torch.linspace(vmin, vmax, atoms, device=dev)
+    state = {"draw": 0}
+
+    def learn(replay, batch):
+        s, a, r, s2, done = replay.sample(batch, seed=1, draw=state["draw"])
+        state["draw"] += 1
+        with torch.no_grad():
+            nd = target(s2) * support
+            nd = nd[torch.arange(batch, device=dev), nd.sum(2).max(1)[1]]
+            tz = (r[:, None] + (1 - done[:, None]) * 0.99 * support[None]).clamp(vmin, vmax)
+            b = (tz - vmin) / ((vmax - vmin) / (atoms - 1))
+            lo, up = b.floor().long(), b.ceil().long()
+            off = (torch.arange(batch, device=dev) * atoms)[:, None]
+            proj = torch.zeros(batch * atoms, device=dev)
+            proj.index_add_(0, (lo + off).view(-1), (nd * (up.float() - b)).view(-1))
+            proj.index_add_(0, (up + off).view(-1), (nd * (b - lo.float())).view(-1))
+        dist = current(s)[torch.arange(batch, device=dev), a]
+        dist.data.clamp_(0.01, 0.99)
+        loss = -(proj.view(batch, atoms) * dist.log()).sum(1).mean()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        current.reset_noise()
+        target.reset_noise()
+
+    return current, learn
+
+
+def timed(torch, fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3  # microseconds
+
+
+def kernel_breakdown(torch, learner, updates=20):
+    try:
+        from torch.profiler import ProfilerActivity, profile
+
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            learner.learn(updates)
+            torch.cuda.synchronize()
+        rows = {}
+        for ev in prof.events():
+            m = re.search(r"(rl_\w+_kernel|learn_\w+_kernel|rainbow_pack_kernel)", ev.name)
+            if not m:
+                continue
+            t = getattr(ev, "device_time", None)
+            if t is None:
+                t = getattr(ev, "cuda_time", 0.0)
+            if not t:
+                continue
+            cnt, tot = rows.get(m.group(1), (0, 0.0))
+            rows[m.group(1)] = (cnt + 1, tot + float(t))
+        if not rows:
+            return None
+        return {k: {"per_update": c / updates, "mean_us": tot / c} for k, (c, tot) in sorted(rows.items())}
+    except Exception as e:  # noqa: BLE001 - the breakdown is optional, the timings are not
+        return {"error": repr(e)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rainbow_learn_bench.json"))
+    ap.add_argument("--updates", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    args = ap.parse_args()
+
+    import torch
+
+    from merging_gym import RainbowLearner, RainbowReplay, _native
+
+    if not torch.cuda.is_available():
+        sys.exit("rainbow_learn_bench needs the GPU: a time taken elsewhere says nothing")
+    dev = torch.device("cuda", 0)
+    result = {"device": torch.cuda.get_device_name(0), "build": _native.build_info(), "updates": args.updates,
+              "warmup": args.warmup, "launches_per_update": LAUNCHES, "batches": {}}
+    for batch in BATCHES:
+        torch.manual_seed(0)
+        replay = RainbowReplay(10000, device=dev)
+        replay.memory.copy_(torch.rand(replay.memory.shape, device=dev) * 10.0)
+        replay.memory[:, 10] = torch.randint(0, 5, (10000,), device=dev).float()
+        replay.memory[:, 22] = torch.randint(0, 2, (10000,), device=dev).float()
+        replay._counter.fill_(10000)
+        net, torch_learn = torch_rainbow(torch, dev)
+        learner = RainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, replay, batch_size=batch)
+        learner.learn(args.warmup)
+        for _ in range(args.warmup):
+            torch_learn(replay, batch)
+        ours, ref = [], []
+        for _ in range(args.repeats):  # alternating, so drift of the shared machine hits both
+            ours.append(timed(torch, lambda: learner.learn(args.updates)) / args.updates)
+            ref.append(timed(torch, lambda: [torch_learn(replay, batch) for _ in range(args.updates)]) / args.updates)
+        entry = {"batch": batch, "ours_us": min(ours), "ours_us_runs": ours, "torch_us": min(ref), "torch_us_runs": ref,
+                 "launches": LAUNCHES, "per_launch_us": min(ours) / LAUNCHES,
+                 "speedup_vs_torch": min(ref) / min(ours), "kernels": kernel_breakdown(torch, learner)}
+        result["batches"][f"b{batch}"] = entry
+        print(json.dumps({f"b{batch}": entry}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {args.out}")
+
+
+if __name__ == "__main__":
+    main()
