@@ -37,12 +37,13 @@
 #include "mg_rollout_hdqn.h"    // the h-DQN acting loop: hdqn_rollout_kernel
 #include "mg_rollout_rainbow.h" // Rainbow's acting loop: rainbow_rollout_kernel
 #include "mg_reset_observe.h"   // reset_kernel, observe_kernel
-#include "mg_replay.h"          // the replay ring: scan, write and sample kernels
+#include "mg_replay.h"          // the replay ring: scan, write and sample kernels, counter_add_kernel
 #include "mg_launch.h"          // error text, armed events, argument checks, launch helpers
 #include "mg_mpc_qp.h"          // mpc_qp_constants (host only)
 #include "mg_stats_reduce.h"    // the fixed-order statistics reduction, goal_status_kernel
 #include "mg_host_env.h"        // the CPU single-env path
-#include "mg_learn.h"           // DQN.learn: the minibatch update kernels and their host twin
+#include "mg_learn_core.h"      // the fixed-order fp32 primitives both learners share, learn_bwd_kernel
+#include "mg_learn.h"           // DQN.learn: the minibatch update kernels, their launch order and host twin
 #include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
 
 extern "C" {
@@ -490,22 +491,10 @@ int mg_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int
   hipStream_t st = static_cast<hipStream_t>(stream);
   Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
   const LearnLayout O = learn_layout(in_dim, out_dim);
-  const int P = O.total;
   for (int32_t u = 0; u < num_updates; ++u) {
     const uint64_t t = first_update + static_cast<uint64_t>(u);
-    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), loss_out ? loss_out + u : nullptr,
-                     rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
-    if (t % static_cast<uint64_t>(hyper->target_period) == 0)
-      hipLaunchKernelGGL(learn_copy_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L.eval, L.target, P);
-    hipLaunchKernelGGL(learn_l1_kernel, dim3(grid_blocks(int64_t{3} * batch * kLH1)), dim3(kBlock), 0, st, L);
-    hipLaunchKernelGGL(learn_l2_kernel, dim3((kLH2 + kLTileJ - 1) / kLTileJ, (batch + kLTileB - 1) / kLTileB, 3),
-                       dim3(kLTileJ * kLTileB), 0, st, L);
-    hipLaunchKernelGGL(learn_l3_kernel, dim3((batch + kLRows3 - 1) / kLRows3), dim3(32 * kLRows3), 0, st, L);
-    for (int layer = 3; layer >= 1; --layer) {
-      const LearnBwd G = learn_bwd_layer(L, layer);
-      hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
-    }
-    hipLaunchKernelGGL(learn_adam_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L, P);
+    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), u, loss_out, rows_out);
+    launch_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0, st);
   }
   if (packed_out)  // the acting kernels' layout of the new eval net, on the same stream
     return mg_qnet_pack(L.eval + O.w1, L.eval + O.b1, L.eval + O.w2, L.eval + O.b2, L.eval + O.w3, L.eval + O.b3,
@@ -524,8 +513,7 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
   const LearnLayout O = learn_layout(in_dim, out_dim);
   for (int32_t u = 0; u < num_updates; ++u) {
     const uint64_t t = first_update + static_cast<uint64_t>(u);
-    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), loss_out ? loss_out + u : nullptr,
-                     rows_out ? rows_out + static_cast<int64_t>(u) * batch * row_floats : nullptr);
+    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), u, loss_out, rows_out);
     host_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0);
   }
   g_err[0] = '\0';
@@ -649,7 +637,7 @@ int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, co
   R.total = n * num_steps;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
-  hipLaunchKernelGGL(rl_counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
   return finish_launch("mg_rainbow_replay_store");
 }
 
@@ -669,34 +657,16 @@ int mg_rainbow_learn(float* learner, const float* rows, const uint64_t* counter,
     return e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
-  const unsigned eff_blocks = grid_blocks(2 * kRlEps);
   // the effective weights of the stored noise; every update's last launch leaves the next one's
-  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(eff_blocks), dim3(kBlock), 0, st, L, 0);
+  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 0);
   for (int32_t u = 0; u < num_updates; ++u) {
     rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
                              noise, loss_out, rows_out, proj_out, grads_out);
-    hipLaunchKernelGGL(rl_forward_kernel, dim3(batch), dim3(2 * kRlThreads), 0, st, L);
-    const LearnBwd G0 = rl_bwd_layer(L, 0), G1 = rl_bwd_layer(L, 1), G2 = rl_bwd_layer(L, 2), G3 = rl_bwd_layer(L, 3);
-    hipLaunchKernelGGL(rl_bwd_heads_kernel, dim3(grid_blocks(learn_bwd_items(G0) + learn_bwd_items(G1))), dim3(kBlock),
-                       0, st, G0, G1);
-    hipLaunchKernelGGL(rl_bwd_streams_kernel, dim3(grid_blocks(rl_bwd_streams_items(L, G2, G3))), dim3(kBlock), 0, st, L,
-                       G2, G3);
-    for (int which = 4; which < 6; ++which) {
-      const LearnBwd G = rl_bwd_layer(L, which);
-      hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
-    }
-    hipLaunchKernelGGL(rl_adam_kernel, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
-    hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(eff_blocks), dim3(kBlock), 0, st, L, 1);
+    launch_rainbow_learn_update(L, st);
   }
-  if (packed_out) {  // the acting kernels' layout of the current model's effective weights, on the same stream
-    const float* e = L.eff;
-    const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
-    const RbTensors T{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
-                      e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
-                      e + A1.e, e + A1.e + A1.out * kRbHS, e + A2.e, e + A2.e + A2.out * kRbHS, learner + kRlOffZ};
-    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st, T,
-                       static_cast<uint8_t*>(packed_out));
-  }
+  if (packed_out)  // the acting kernels' layout of the current model's effective weights, on the same stream
+    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st,
+                       rainbow_learn_tensors(learner, L.eff), static_cast<uint8_t*>(packed_out));
   return finish_launch("mg_rainbow_learn");
 }
 

@@ -6,6 +6,7 @@
 #include "mg_common.h"
 #include "mg_env.h"
 #include "mg_launch.h"
+#include "mg_learn_core.h"
 #include "mg_qnet.h"
 
 namespace {
@@ -14,7 +15,8 @@ namespace {
 // scripts/main.py:122-157 (DQN.learn), hdqn.py:186-221 (HDQN.learn), :104-139 (Goal_DQN.learn): the
 // same code on Net(in, out) with hidden widths 200 / 100 (main.py:30-47). All arithmetic is fp32 in
 // the fixed order include/merging_hip.h documents at mg_dqn_learn: every dot product a sequential
-// fmaf chain, no float atomics, nothing that depends on the grid. One update is seven launches:
+// fmaf chain, no float atomics, nothing that depends on the grid (the shared primitives are
+// mg_learn_core.h's). One update is seven launches, in launch_learn_update's order:
 //   learn_l1_kernel    minibatch rows (the draw of mg_replay_sample) -> scratch, layer 1 of the
 //                      three passes: eval(s), eval(s'), target(s')
 //   learn_l2_kernel    layer 2 of the three passes, W2 and the inputs tiled through LDS
@@ -27,9 +29,6 @@ constexpr int kLH1 = 200;  // main.py:34
 constexpr int kLH2 = 100;  // main.py:36
 constexpr int kLTileJ = 32;  // learn_l2_kernel: units per block
 constexpr int kLTileB = 8;   //                  rows per block
-constexpr int kLBatch = 16;  // loads a chain issues together before it consumes them, in order: a
-                             // one-by-one chain waits a memory latency per term (166 us per update
-                             // at batch 128 before)
 constexpr int kLRows3 = 8;   // learn_l3_kernel: rows per block (32 slots each: 3 passes x out <= 24 used)
 
 // Offsets (floats) of torch's parameter order inside one block of the learner buffer.
@@ -54,8 +53,6 @@ struct LearnScratch {
   int64_t rows, h1, h2, d, dq, dh2, dh1, g, total;
 };
 
-MG_HD int64_t learn_round4(int64_t n) { return (n + 3) & ~int64_t{3}; }
-
 MG_HD LearnScratch learn_scratch(int64_t B, int in, int out) {
   LearnScratch S;
   S.rows = 0;
@@ -69,10 +66,6 @@ MG_HD LearnScratch learn_scratch(int64_t B, int in, int out) {
   S.total = S.g + learn_round4(learn_layout(in, out).total);
   return S;
 }
-
-struct LearnAdam {  // one update's scalars: doubles on the host, each rounded to fp32 once
-  float b1, omb1, b2, omb2, step, bc2s, eps;
-};
 
 // Everything one update's launches (or the host loops) read.
 struct Learn {
@@ -101,100 +94,6 @@ struct Learn {
 };
 
 // ---------------------------------------------------------------------------- per-element functions
-// Slot of minibatch row b: mg_replay_sample's draw (replay_sample_kernel), word x of
-// Philox4x32-10(key = seed, counter = (b, draw)) scaled to [0, m).
-MG_HD uint64_t learn_slot(uint64_t b, uint64_t draw, uint64_t seed, uint64_t m) {
-#ifdef __HIP_DEVICE_COMPILE__
-  const uint4 u = philox4x32_10(make_uint4(static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32),
-                                           static_cast<uint32_t>(draw), static_cast<uint32_t>(draw >> 32)),
-                                static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-  return (static_cast<uint64_t>(u.x) * m) >> 32;
-#else
-  uint32_t c0 = static_cast<uint32_t>(b), c1 = static_cast<uint32_t>(b >> 32);
-  uint32_t c2 = static_cast<uint32_t>(draw), c3 = static_cast<uint32_t>(draw >> 32);
-  uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const uint32_t n0 = static_cast<uint32_t>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<uint32_t>(p0 >> 32) ^ c3 ^ k1;
-    c1 = static_cast<uint32_t>(p1);
-    c3 = static_cast<uint32_t>(p0);
-    c0 = n0;
-    c2 = n2;
-  }
-  return (static_cast<uint64_t>(c0) * m) >> 32;
-#endif
-}
-
-// Rows the draw chooses among: the capacity, or with filled_only the rows stored so far (>= 1).
-MG_HD uint64_t learn_rows_live(int64_t cap, const uint64_t* counter, int32_t filled_only) {
-  uint64_t m = static_cast<uint64_t>(cap);
-  if (filled_only) {
-    const uint64_t c = *counter;
-    m = c < m ? c : m;
-    if (m == 0) m = 1;
-  }
-  return m;
-}
-
-// y = fmaf(x[K-1], w[K-1], ... fmaf(x[0], w[0], bias)), k ascending.
-MG_HD float learn_fwd(const float* x, const float* w, float bias, int K) {
-  float acc = bias;
-  int k = 0;
-  for (; k + kLBatch <= K; k += kLBatch) {  // the batch's loads issued together, the chain's order kept
-    float xv[kLBatch], wv[kLBatch];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) xv[u] = x[k + u], wv[u] = w[k + u];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) acc = fmaf(xv[u], wv[u], acc);
-  }
-  for (; k < K; ++k) acc = fmaf(x[k], w[k], acc);
-  return acc;
-}
-
-MG_HD float learn_relu(float y) { return y > 0.0f ? y : 0.0f; }
-
-// fmaf chain over i ascending of a[i sa] b[i sb], from +0 (weight and input gradients).
-MG_HD float learn_chain(const float* a, int64_t sa, const float* b, int64_t sb, int n) {
-  float acc = 0.0f;
-  int i = 0;
-  for (; i + kLBatch <= n; i += kLBatch) {
-    float av[kLBatch], bv[kLBatch];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) av[u] = a[(i + u) * sa], bv[u] = b[(i + u) * sb];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) acc = fmaf(av[u], bv[u], acc);
-  }
-  for (; i < n; ++i) acc = fmaf(a[i * sa], b[i * sb], acc);
-  return acc;
-}
-
-// Sequential sum over i ascending of a[i sa], from +0 (bias gradients).
-MG_HD float learn_sum(const float* a, int64_t sa, int n) {
-  float acc = 0.0f;
-  int i = 0;
-  for (; i + kLBatch <= n; i += kLBatch) {
-    float av[kLBatch];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) av[u] = a[(i + u) * sa];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) acc = acc + av[u];
-  }
-  for (; i < n; ++i) acc = acc + a[i * sa];
-  return acc;
-}
-
-// The row's action column truncated to int (main.py:133 astype(int)), kept inside 0..out-1 (the
-// reference's gather would raise outside; NaN gives 0).
-MG_HD int learn_action(float a, int out) {
-  if (!(a >= 0.0f)) return 0;
-  if (a >= static_cast<float>(out)) return out - 1;
-  return static_cast<int>(a);
-}
-
 // d = q_eval(s)[a] - (r + gamma target(s')[argmax eval(s')]) (main.py:144-152), lowest index on ties.
 MG_HD float learn_td(const float* qe, const float* qe2, const float* qt2, int out, int a, float r, float gamma) {
   int am = 0;
@@ -202,29 +101,6 @@ MG_HD float learn_td(const float* qe, const float* qe2, const float* qt2, int ou
     if (qe2[j] > qe2[am]) am = j;
   const float t = r + gamma * qt2[am];
   return qe[a] - t;
-}
-
-// loss = (sum over b ascending of d[b] d[b], from +0) (1 / B) (nn.MSELoss, main.py:153).
-MG_HD float learn_loss(const float* d, int B, float inv_b) {
-  float acc = 0.0f;
-  int b = 0;
-  for (; b + kLBatch <= B; b += kLBatch) {
-    float dv[kLBatch];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) dv[u] = d[b + u];
-#pragma unroll
-    for (int u = 0; u < kLBatch; ++u) acc = acc + dv[u] * dv[u];
-  }
-  for (; b < B; ++b) acc = acc + d[b] * d[b];
-  return acc * inv_b;
-}
-
-// torch.optim.Adam's single-tensor step (main.py:96, :157), every operation rounded once.
-MG_HD void learn_adam(float& p, float& m, float& v, float g, const LearnAdam& A) {
-  m = fmaf(A.omb1, g, A.b1 * m);
-  v = fmaf(A.omb2 * g, g, A.b2 * v);
-  const float den = sqrtf(v) / A.bc2s + A.eps;
-  p = p - A.step * (m / den);
 }
 
 // ---------------------------------------------------------------------------- per-output steps
@@ -263,46 +139,6 @@ MG_HD void learn_td_at(const Learn& L, int b, int j, const float* q) {
   L.dq[b * kLMaxOut + j] = j == a ? d * L.two_inv_b : 0.0f;
 }
 
-// One layer's backward pass: y[b, j] = sum_k x[b, k] W[j, k] + bias[j] with dy given.
-struct LearnBwd {
-  const float* dy;  // [B, nJ] with row stride sdy
-  const float* x;   // [B, nK] with row stride sx: the layer's input
-  const float* W;   // [nJ, nK] (eval)
-  float* gW;        // [nJ, nK]
-  float* gb;        // [nJ]
-  float* dx;        // [B, nK] = (dy W) where x > 0, or NULL (layer 1)
-  const float* d;   // with loss_out: the launch that also sums the loss
-  float* loss_out;
-  float inv_b;
-  int32_t sdy, sx, nJ, nK, B;
-};
-
-MG_HD int64_t learn_bwd_grads(const LearnBwd& G) { return static_cast<int64_t>(G.nJ) * (G.nK + 1); }
-MG_HD int64_t learn_bwd_items(const LearnBwd& G) {
-  return learn_bwd_grads(G) + (G.dx ? static_cast<int64_t>(G.B) * G.nK : 0) + 1;
-}
-
-MG_HD void learn_bwd_at(const LearnBwd& G, int64_t idx) {
-  const int64_t ng = learn_bwd_grads(G);
-  if (idx < ng) {
-    const int j = static_cast<int>(idx / (G.nK + 1)), k = static_cast<int>(idx - static_cast<int64_t>(j) * (G.nK + 1));
-    if (k < G.nK)
-      G.gW[j * G.nK + k] = learn_chain(G.dy + j, G.sdy, G.x + k, G.sx, G.B);
-    else
-      G.gb[j] = learn_sum(G.dy + j, G.sdy, G.B);
-    return;
-  }
-  idx -= ng;
-  const int64_t nx = G.dx ? static_cast<int64_t>(G.B) * G.nK : 0;
-  if (idx < nx) {
-    const int b = static_cast<int>(idx / G.nK), k = static_cast<int>(idx - static_cast<int64_t>(b) * G.nK);
-    const float v = learn_chain(G.dy + static_cast<int64_t>(b) * G.sdy, 1, G.W + k, G.nK, G.nJ);
-    G.dx[idx] = G.x[static_cast<int64_t>(b) * G.sx + k] > 0.0f ? v : 0.0f;
-    return;
-  }
-  if (idx == nx && G.loss_out) *G.loss_out = learn_loss(G.d, G.B, G.inv_b);
-}
-
 // The three backward launches of one update, layer 3 first.
 MG_HD LearnBwd learn_bwd_layer(const Learn& L, int layer) {
   const LearnLayout O = learn_layout(L.in, L.out);
@@ -331,11 +167,6 @@ MG_HD LearnBwd learn_bwd_layer(const Learn& L, int layer) {
 MG_HD void learn_adam_at(const Learn& L, int64_t i) { learn_adam(L.eval[i], L.m[i], L.v[i], L.g[i], L.A); }
 
 // ---------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(kBlock) void learn_copy_kernel(const float* src, float* dst, int n) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) dst[i] = src[i];
-}
-
 __global__ __launch_bounds__(kBlock) void learn_l1_kernel(const Learn L) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (idx >= static_cast<int64_t>(3) * L.B * kLH1) return;
@@ -375,11 +206,6 @@ __global__ __launch_bounds__(32 * kLRows3) void learn_l3_kernel(const Learn L) {
   if (b < L.B && slot < L.out) learn_td_at(L, b, slot, q[rb]);
 }
 
-__global__ __launch_bounds__(kBlock) void learn_bwd_kernel(const LearnBwd G) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (idx < learn_bwd_items(G)) learn_bwd_at(G, idx);
-}
-
 __global__ __launch_bounds__(kBlock) void learn_adam_kernel(const Learn L, int n) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n) learn_adam_at(L, i);
@@ -396,13 +222,9 @@ int check_learn(const char* what, const float* learner, const float* rows, const
   if (int e = check_net_dims(what, in_dim, out_dim)) return e;
   if (row_floats != 2 * in_dim + 2)
     return fail(hipErrorInvalidValue, "%s: row_floats must be 2 * in_dim + 2", what);
-  if (batch < 1 || batch > 1024) return fail(hipErrorInvalidValue, "%s: need 1 <= batch <= 1024", what);
-  if (capacity < 1 || capacity > (int64_t{1} << 32))
-    return fail(hipErrorInvalidValue, "%s: need 1 <= capacity <= 2^32", what);
-  if (num_updates < 0) return fail(hipErrorInvalidValue, "%s: num_updates < 0", what);
+  if (int e = check_learn_sizes(what, batch, capacity, num_updates)) return e;
   if (hyper->target_period < 1) return fail(hipErrorInvalidValue, "%s: target_period must be >= 1", what);
-  if (!(hyper->beta1 >= 0.0 && hyper->beta1 < 1.0 && hyper->beta2 >= 0.0 && hyper->beta2 < 1.0))
-    return fail(hipErrorInvalidValue, "%s: need 0 <= beta1 < 1 and 0 <= beta2 < 1", what);
+  if (int e = check_adam_betas(what, hyper)) return e;
   if (misaligned(learner, 15) || misaligned(scratch, 15) || misaligned(packed_out, 15) || misaligned(rows, 7) ||
       misaligned(counter, 7) || misaligned(loss_out, 3) || misaligned(rows_out, 3))
     return fail(hipErrorInvalidValue,
@@ -434,20 +256,30 @@ Learn make_learn(float* learner, const float* rows, const uint64_t* counter, int
   return L;
 }
 
-// Update number t's fields (t counted from 0; Adam's step count is t + 1): the scalars in double,
-// libm pow as Python's float ** int, each rounded to fp32 once.
-void learn_set_update(Learn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw, float* loss_out, float* rows_out) {
-  const double step = static_cast<double>(t + 1);
+// Update number u of a call: its draw, optional outputs and Adam's step t + 1 (t = first_update + u).
+void learn_set_update(Learn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw, int32_t u, float* loss_out,
+                      float* rows_out) {
+  L.A = learn_adam_scalars(h, t);
   L.draw = draw;
-  L.loss_out = loss_out;
-  L.rows_out = rows_out;
-  L.A.b1 = static_cast<float>(h->beta1);
-  L.A.omb1 = static_cast<float>(1.0 - h->beta1);
-  L.A.b2 = static_cast<float>(h->beta2);
-  L.A.omb2 = static_cast<float>(1.0 - h->beta2);
-  L.A.step = static_cast<float>(h->lr / (1.0 - std::pow(h->beta1, step)));
-  L.A.bc2s = static_cast<float>(std::sqrt(1.0 - std::pow(h->beta2, step)));
-  L.A.eps = static_cast<float>(h->eps);
+  L.loss_out = loss_out ? loss_out + u : nullptr;
+  L.rows_out = rows_out ? rows_out + static_cast<int64_t>(u) * L.B * L.rf : nullptr;
+}
+
+// One update on the device (mg_dqn_learn), after learn_set_update: the launch order that
+// host_learn_update below restates loop for loop.
+void launch_learn_update(const Learn& L, const LearnLayout& O, bool sync_target, hipStream_t st) {
+  const int P = O.total;
+  if (sync_target)
+    hipLaunchKernelGGL(learn_copy_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L.eval, L.target, P);
+  hipLaunchKernelGGL(learn_l1_kernel, dim3(grid_blocks(int64_t{3} * L.B * kLH1)), dim3(kBlock), 0, st, L);
+  hipLaunchKernelGGL(learn_l2_kernel, dim3((kLH2 + kLTileJ - 1) / kLTileJ, (L.B + kLTileB - 1) / kLTileB, 3),
+                     dim3(kLTileJ * kLTileB), 0, st, L);
+  hipLaunchKernelGGL(learn_l3_kernel, dim3((L.B + kLRows3 - 1) / kLRows3), dim3(32 * kLRows3), 0, st, L);
+  for (int layer = 3; layer >= 1; --layer) {
+    const LearnBwd G = learn_bwd_layer(L, layer);
+    hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
+  }
+  hipLaunchKernelGGL(learn_adam_kernel, dim3(grid_blocks(P)), dim3(kBlock), 0, st, L, P);
 }
 
 // One update on the host (mg_host_dqn_learn), after learn_set_update: the kernels' per-item

@@ -7,8 +7,9 @@
 #include "mg_common.h"
 #include "mg_env.h"
 #include "mg_launch.h"
-#include "mg_learn.h"
+#include "mg_learn_core.h"
 #include "mg_rainbow.h"
+#include "mg_replay.h"
 
 namespace {
 
@@ -46,9 +47,6 @@ __global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const
 #pragma unroll
   for (int k = 0; k < kRlRow / 2; ++k) d[k] = f32x2{v[2 * k], v[2 * k + 1]};
 }
-
-// after every thread of the store has read the old counter: the same stream orders it
-__global__ void rl_counter_add_kernel(uint64_t* counter, uint64_t k) { *counter += k; }
 
 // ============================================================================ compute_td_loss
 // scripts/ranbowdqn.py:554-609 on RainbowDQN(10, 5) with 51 atoms, all fp32 in the fixed order
@@ -475,14 +473,10 @@ int check_rainbow_learn(const char* what, const float* learner, const float* row
                         const float* noise, const float* loss_out, const float* rows_out, const float* proj_out,
                         const float* grads_out, const void* packed_out, const void* scratch, size_t scratch_bytes) {
   if (!learner || !rows || !counter || !hyper || !scratch) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
-  if (batch < 1 || batch > 1024) return fail(hipErrorInvalidValue, "%s: need 1 <= batch <= 1024", what);
-  if (capacity < 1 || capacity > (int64_t{1} << 32))
-    return fail(hipErrorInvalidValue, "%s: need 1 <= capacity <= 2^32", what);
-  if (num_updates < 0) return fail(hipErrorInvalidValue, "%s: num_updates < 0", what);
+  if (int e = check_learn_sizes(what, batch, capacity, num_updates)) return e;
   if (num_updates > 0 && !noise)
     return fail(hipErrorInvalidValue, "%s: noise is NULL (num_updates x 2 x 1124 factors)", what);
-  if (!(hyper->beta1 >= 0.0 && hyper->beta1 < 1.0 && hyper->beta2 >= 0.0 && hyper->beta2 < 1.0))
-    return fail(hipErrorInvalidValue, "%s: need 0 <= beta1 < 1 and 0 <= beta2 < 1", what);
+  if (int e = check_adam_betas(what, hyper)) return e;
   if (misaligned(learner, 15) || misaligned(scratch, 15) || misaligned(packed_out, 15) || misaligned(rows, 7) ||
       misaligned(counter, 7) || misaligned(noise, 3) || misaligned(loss_out, 3) || misaligned(rows_out, 3) ||
       misaligned(proj_out, 3) || misaligned(grads_out, 3))
@@ -510,19 +504,41 @@ RLearn make_rainbow_learn(float* learner, const float* rows, const uint64_t* cou
   return L;
 }
 
-// Update number u of a call: its draw, factors, optional outputs and (through a Learn, whose Adam scalars
-// learn_set_update computes) Adam's step first_update + u + 1.
+// Update number u of a call: its draw, factors, optional outputs and Adam's step t + 1 (t = first_update + u).
 void rainbow_learn_set_update(RLearn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw, int32_t u, const float* noise,
                               float* loss_out, float* rows_out, float* proj_out, float* grads_out) {
-  Learn tmp{};
-  learn_set_update(tmp, h, t, draw, nullptr, nullptr);
-  L.A = tmp.A;
+  L.A = learn_adam_scalars(h, t);
   L.draw = draw;
   L.noise = noise + static_cast<int64_t>(u) * 2 * kRlFactors;
   L.loss_out = loss_out ? loss_out + u : nullptr;
   L.rows_out = rows_out ? rows_out + static_cast<int64_t>(u) * L.B * kRlRow : nullptr;
   L.proj_out = proj_out ? proj_out + static_cast<int64_t>(u) * L.B * kRbAtoms : nullptr;
   L.grads_out = grads_out ? grads_out + static_cast<int64_t>(u) * kRlParams : nullptr;
+}
+
+// One update on the device (mg_rainbow_learn), after rainbow_learn_set_update: the launch order that
+// host_rainbow_learn_update below restates loop for loop (the last launch leaves the next update's weights).
+void launch_rainbow_learn_update(const RLearn& L, hipStream_t st) {
+  hipLaunchKernelGGL(rl_forward_kernel, dim3(L.B), dim3(2 * kRlThreads), 0, st, L);
+  const LearnBwd G0 = rl_bwd_layer(L, 0), G1 = rl_bwd_layer(L, 1), G2 = rl_bwd_layer(L, 2), G3 = rl_bwd_layer(L, 3);
+  hipLaunchKernelGGL(rl_bwd_heads_kernel, dim3(grid_blocks(learn_bwd_items(G0) + learn_bwd_items(G1))), dim3(kBlock),
+                     0, st, G0, G1);
+  hipLaunchKernelGGL(rl_bwd_streams_kernel, dim3(grid_blocks(rl_bwd_streams_items(L, G2, G3))), dim3(kBlock), 0, st, L,
+                     G2, G3);
+  for (int which = 4; which < 6; ++which) {
+    const LearnBwd G = rl_bwd_layer(L, which);
+    hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
+  }
+  hipLaunchKernelGGL(rl_adam_kernel, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
+  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 1);
+}
+
+// What rainbow_pack_kernel packs for acting: the current model's plain layers, effective weights e = L.eff, support.
+RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
+  const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
+  return RbTensors{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
+                   e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
+                   e + A1.e, e + A1.e + A1.out * kRbHS, e + A2.e, e + A2.e + A2.out * kRbHS, learner + kRlOffZ};
 }
 
 // One update on the host (mg_host_rainbow_learn): the kernels' per-item functions in the kernels' order.

@@ -1,4 +1,4 @@
-// mg_replay.h -- the DQN replay ring: ReplayIn, ReplayScratch, the scan, write and sample kernels.
+// mg_replay.h -- the DQN replay ring: ReplayIn, ReplayScratch, the scan, write and sample kernels, counter_add_kernel.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -279,5 +279,9 @@ __global__ __launch_bounds__(kBlock) void replay_sample_kernel(const float* rows
   f32x2* dst = reinterpret_cast<f32x2*>(out + b * row_floats);
   for (int k = 0; k < row_floats / 2; ++k) dst[k] = src[k];
 }
+
+// memory_counter += k for the stores that keep every transition, so need no scan (the fused goal ring, Rainbow's
+// rows): launched behind the store, after every thread of it has read the old counter; the stream orders it
+__global__ void counter_add_kernel(uint64_t* counter, uint64_t k) { *counter += k; }
 
 }  // namespace

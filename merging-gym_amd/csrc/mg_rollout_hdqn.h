@@ -1,4 +1,4 @@
-// mg_rollout_hdqn.h -- the h-DQN acting loop: counter_add_kernel, HRollout, fresh_goal_words, hdqn_rollout_kernel.
+// mg_rollout_hdqn.h -- the h-DQN acting loop: HRollout, fresh_goal_words, hdqn_rollout_kernel.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -10,9 +10,6 @@
 #include "mg_wave_out.h"
 
 namespace {
-
-// memory_counter += k (the fused goal ring's stores are all kept: no scan)
-__global__ void counter_add_kernel(uint64_t* counter, uint64_t k) { *counter += k; }
 
 // ============================================================================ h-DQN acting loop
 // hdqn.py's inner loop (scripts/hdqn.py:280-323) in one launch: Goal_DQN's meta-net picks the

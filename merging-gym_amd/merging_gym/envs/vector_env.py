@@ -36,6 +36,7 @@ import os
 import numpy as np
 
 from .. import spaces
+from .._device import U64, cuda_device, ptr, raw_stream
 
 _OBS_DIM = 10
 # The streamed per-env arrays (state + one step's outputs) are carved from one allocation, each
@@ -73,9 +74,7 @@ class MergeVecEnv:
         self._torch = torch
         self._nat = _native
         self.num_envs = int(num_envs)
-        self.device = torch.device(device if device is not None else "cuda", )
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(torch, device)
         self.autoreset = bool(autoreset)
         self.env_offset = int(env_offset)
         self.params = _native.default_params()
@@ -133,7 +132,6 @@ class MergeVecEnv:
         # hdqn.py:330), kept by the fused policy rollouts (rollout_qnet, rollout_hdqn)
         self.q_eval = self._ep_stats[:, 7] if episode_stats else None
 
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         self._state = _native.State(*(ptr(t) for t in (self.p1, self.v1, self.p2, self.v2,
                                                         self.ret1, self.ret2, self.tf)))
         packed = self.flags is not None
@@ -169,7 +167,7 @@ class MergeVecEnv:
         """Raw handle of torch's current stream on this device (honours `torch.cuda.stream(...)`)."""
         if self._raw_stream is not None:
             return self._raw_stream(self.device.index)
-        return self._torch.cuda.current_stream(self.device).cuda_stream
+        return raw_stream(self._torch, self.device)
 
     def _actions(self, a, buf, allow_none: bool):
         torch = self._torch
@@ -267,7 +265,7 @@ class MergeVecEnv:
         rc = self._nat.lib.mg_step_random(
             self._p_ref, self._s_ref, self._a1_ptr if record_actions else None,
             self._a2_ptr if record_actions else None, self._o_ref, self._st_ref, self.num_envs,
-            self.env_offset, seed & 0xFFFFFFFFFFFFFFFF, k & 0xFFFFFFFFFFFFFFFF,
+            self.env_offset, seed & U64, k & U64,
             1 if opponent_random else 0, self._flags, self._stream())
         self._nat.check(rc, "mg_step_random")
         self._step_idx = k + 1
@@ -296,7 +294,7 @@ class MergeVecEnv:
             traj = buf["_traj"] if t0 == 0 else self._traj_slice(buf, t0)
             rc = nat.lib.mg_rollout_random(
                 self._p_ref, self._s_ref, ctypes.byref(traj), self._st_ref, n, self.env_offset,
-                seed & 0xFFFFFFFFFFFFFFFF, (k0 + t0) & 0xFFFFFFFFFFFFFFFF, tc, 1 if opponent_random else 0,
+                seed & U64, (k0 + t0) & U64, tc, 1 if opponent_random else 0,
                 self._flags, self._stream())
             nat.check(rc, "mg_rollout_random")
         self._step_idx = k0 + T
@@ -305,10 +303,10 @@ class MergeVecEnv:
     def _traj_slice(self, buf, t0):
         """mg_traj of the trajectory buffers from step t0 on (a chunk of a long rollout)."""
         n = self.num_envs
-        ptr = lambda t, row: None if t is None else t.data_ptr() + t0 * row  # noqa: E731
-        return self._nat.Traj(ptr(buf["obs"], n * _OBS_DIM * 4), ptr(buf["rew"], n * 8), None, None, None, None,
-                              ptr(buf["final_observation"], n * _OBS_DIM * 4), ptr(buf["won_mask"], (n + 63) // 64 * 8),
-                              ptr(buf["flags"], n * 4))
+        at = lambda t, row: None if t is None else t.data_ptr() + t0 * row  # noqa: E731
+        return self._nat.Traj(at(buf["obs"], n * _OBS_DIM * 4), at(buf["rew"], n * 8), None, None, None, None,
+                              at(buf["final_observation"], n * _OBS_DIM * 4), at(buf["won_mask"], (n + 63) // 64 * 8),
+                              at(buf["flags"], n * 4))
 
     def _traj(self, T, final_observation, won_mask=True):
         """[T, N, ...] trajectory buffers, reused while T and the output choices stay the same."""
@@ -328,7 +326,6 @@ class MergeVecEnv:
                                                     device=dev) if final_observation else None),
                    "won_mask": (torch.zeros((T, (n + 63) // 64), dtype=torch.int64, device=dev)
                                 if won_mask else None)}
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
             buf["_traj"] = nat.Traj(ptr(buf["obs"]), ptr(buf["rew"]), None, None, None, None,
                                     ptr(buf["final_observation"]), ptr(buf["won_mask"]), ptr(flags))
             buf["_result"] = {"obs": buf["obs"], "rew": buf["rew"], "done": flags[..., 2].view(torch.bool),
@@ -364,7 +361,7 @@ class MergeVecEnv:
         buf = self._traj(T, final_observation, won_mask)
         rc = nat.lib.mg_rollout_qnet(
             self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, n, self.env_offset,
-            seed & 0xFFFFFFFFFFFFFFFF, k0 & 0xFFFFFFFFFFFFFFFF, T, qnet.packed.data_ptr(), qnet.out_dim,
+            seed & U64, k0 & U64, T, qnet.packed.data_ptr(), qnet.out_dim,
             greedy_threshold(episilo), mode, greedy_threshold(opp_episilo),
             None if opp_net is None else opp_net.packed.data_ptr(), self._flags, self._stream())
         nat.check(rc, "mg_rollout_qnet")
@@ -457,7 +454,7 @@ class MergeVecEnv:
         rc = nat.lib.mg_rollout_hdqn(
             self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), ctypes.byref(hb["_hm" if goal_memory else "_h"]),
             self._st_ref, self.hdqn_goal.data_ptr(), None if gop is None else gop.data_ptr(),
-            self.hdqn_ext.data_ptr(), n, self.env_offset, seed & 0xFFFFFFFFFFFFFFFF, k0 & 0xFFFFFFFFFFFFFFFF,
+            self.hdqn_ext.data_ptr(), n, self.env_offset, seed & U64, k0 & U64,
             T, meta.packed.data_ptr(), meta.out_dim, lower.packed.data_ptr(), meta.reset_argmax(self.params),
             greedy_threshold(episilo), mode, None if opp_meta is None else opp_meta.packed.data_ptr(),
             None if opp_lower is None else opp_lower.packed.data_ptr(), None if ring is None else ring.memory.data_ptr(),

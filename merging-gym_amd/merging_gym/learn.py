@@ -24,12 +24,14 @@ from __future__ import annotations
 import ctypes
 
 from . import _native
+from ._base import LearnerBase
+from ._device import ptr
 from .policy import QNet
 
 KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "out.weight", "out.bias")
 
 
-class DQNLearner:
+class DQNLearner(LearnerBase):
     def __init__(self, net, ring, lr: float = 0.01, gamma: float = 0.9, batch_size: int = 128,
                  target_period: int = 100, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, device=None):
         """net: a QNet, or a state dict with the reference's keys (fc1.weight ... out.bias); both
@@ -37,17 +39,9 @@ class DQNLearner:
         (24-float rows) implies in_dim 11. lr, gamma, batch_size, target_period: main.py:13-18's LR,
         GAMMA, BATCH_SIZE, Q_NETWORK_ITERATION; betas, eps: Adam's. seed: the key of the minibatch
         draws (update u of the run draws what ring.sample_rows(batch_size, seed, draw=u) returns)."""
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("DQNLearner needs a ROCm GPU; there is no CPU fallback")
-        self._torch = torch
+        super().__init__(ring, "ring", device)
+        torch = self._torch
         self.ring = ring
-        self.device = torch.device(device) if device is not None else ring.device
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self.device != ring.device:
-            raise ValueError(f"the ring lives on {ring.device}, the learner on {self.device}")
         if isinstance(net, QNet):
             if net.device != self.device and torch.device(net.device.type, net.device.index or 0) != self.device:
                 raise ValueError(f"the QNet lives on {net.device}, the learner on {self.device}")
@@ -59,26 +53,18 @@ class DQNLearner:
         if ring.row != 2 * self.in_dim + 2:
             raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
                              f"the ring's have {ring.row}")
-        self.batch_size, self.target_period = int(batch_size), int(target_period)
-        self.hyper = _native.DqnHyper(float(lr), float(gamma), float(betas[0]), float(betas[1]), float(eps),
-                                      self.target_period, 0)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.learn_step_counter = 0  # main.py:90, :127 -- a Python int: no device round trip
-        self.draw_counter = 0        # minibatches drawn so far
-
+        self._state_of = f"a {self.in_dim} -> {self.out_dim} learner"
         nbytes = int(_native.lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
         if nbytes == 0:
             raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
+        self.target_period = int(target_period)
+        sbytes = int(_native.lib.mg_dqn_learn_scratch_bytes(int(batch_size), self.in_dim, self.out_dim))
+        self._setup(batch_size, seed, sbytes, lr, gamma, betas, eps, self.target_period)
         self._P = nbytes // 16
         self._buf = torch.empty(4 * self._P, dtype=torch.float32, device=self.device)
         _native.check(_native.lib.mg_dqn_learner_init(self._buf.data_ptr(), *(t.data_ptr() for t in tensors),
                                                       self.in_dim, self.out_dim, self._stream()),
                       "mg_dqn_learner_init")
-        sbytes = int(_native.lib.mg_dqn_learn_scratch_bytes(self.batch_size, self.in_dim, self.out_dim))
-        if sbytes == 0:
-            raise ValueError("batch_size must be in 1..1024")
-        self._scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=self.device)
-        self._scratch_bytes = sbytes
         # the acting net: its fp32 tensors are views of the eval block, its packed buffer is
         # rewritten by every learn()
         self.qnet = qnet if qnet is not None else QNet(*self._views(0), device=self.device)
@@ -86,9 +72,6 @@ class DQNLearner:
         self.qnet.__dict__.pop("_reset_argmax", None)
 
     # ------------------------------------------------------------------ helpers
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
     def _views(self, block):
         """The six tensors of block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
         flat = self._buf[block * self._P:(block + 1) * self._P]
@@ -124,8 +107,8 @@ class DQNLearner:
                 self._buf.data_ptr(), self.ring.memory.data_ptr(), self.ring._counter.data_ptr(), self.ring.capacity,
                 self.ring.row, self.in_dim, self.out_dim, self.batch_size, U, self.learn_step_counter, self.seed,
                 self.draw_counter, 1 if filled_only else 0, ctypes.byref(self.hyper),
-                None if loss is None else loss.data_ptr(), None if rows is None else rows.data_ptr(),
-                self.qnet.packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes, self._stream())
+                ptr(loss), ptr(rows), self.qnet.packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes,
+                self._stream())
             _native.check(rc, "mg_dqn_learn")
             self.learn_step_counter += U
             self.draw_counter += U
@@ -145,16 +128,10 @@ class DQNLearner:
 
     def state_dict(self):
         """Both nets, Adam's moments and the counters: a run resumed from it continues bit for bit."""
-        return {"learner": self._buf.clone(), "in_dim": self.in_dim, "out_dim": self.out_dim,
-                "learn_step_counter": self.learn_step_counter, "draw_counter": self.draw_counter,
-                "seed": self.seed}
+        return dict(super().state_dict(), in_dim=self.in_dim, out_dim=self.out_dim)
 
     def load_state_dict(self, sd):
-        buf = self._torch.as_tensor(sd["learner"])
-        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim) or buf.numel() != self._buf.numel():
-            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
-        self._buf.copy_(buf.to(self._torch.float32).reshape(-1))
-        self.learn_step_counter = int(sd["learn_step_counter"])
-        self.draw_counter = int(sd["draw_counter"])
-        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim):
+            raise ValueError(f"expected the state of {self._state_of}")
+        super().load_state_dict(sd)
         self._repack()

@@ -25,6 +25,8 @@ from __future__ import annotations
 
 import ctypes
 
+from ._base import LearnerBase, RingBase
+from ._device import ptr
 from .rainbow import NOISY, NUM_ATOMS, PLAIN, SHAPES, RainbowNet
 
 ROW = 24  # [s(10), a, r, s'(10), done, 0]: 8-byte aligned rows mg_replay_sample copies as they are
@@ -104,43 +106,16 @@ def noise_factors(num_updates, generator=None):
     return out.sign().mul_(out.abs().sqrt_())  # _scale_noise's x.sign().mul(x.abs().sqrt()), elementwise
 
 
-class RainbowReplay:
+class RainbowReplay(RingBase):
     """ReplayBuffer(capacity) (:265-323) as a ring of [capacity, 24] fp32 rows on the device; the position is
     a device counter, so stores are stream-ordered and len() synchronises."""
 
     def __init__(self, capacity: int = 10000, device=None):
-        import torch
-
-        from . import _native
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("RainbowReplay needs a ROCm GPU; there is no CPU fallback")
-        if capacity < 1:
-            raise ValueError("capacity must be >= 1")
-        self._torch, self._nat = torch, _native
-        self.capacity = int(capacity)
-        self.row = ROW
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.memory = torch.zeros((self.capacity, ROW), dtype=torch.float32, device=self.device)
-        self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
+        super().__init__(capacity, ROW, device)
 
     def __len__(self):
         """len(replay_buffer) (:278-279). Synchronises the stream."""
         return min(int(self._counter.item()), self.capacity)
-
-    def _f32(self, t, shape):
-        torch = self._torch
-        t = torch.as_tensor(t, device=self.device)
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            t = t.to(torch.float32).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
-        return t
 
     def store(self, obs_first, obs, a1, rew, done=None, final_obs=None, flags=None):
         """Append T steps of N envs ([T, N, ...] tensors; obs_first [N, 10] = the observation before step 0) in
@@ -165,7 +140,6 @@ class RainbowReplay:
         rew = self._f32(rew, (T, n, 2))
         if final_obs is not None:
             final_obs = self._f32(final_obs, (T, n, _OBS))
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         tr = self._nat.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), ptr(a1), ptr(rew), ptr(done), None,
                                    None, None, None, ptr(flags), None)
         rc = self._nat.lib.mg_rainbow_replay_store(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity,
@@ -177,32 +151,19 @@ class RainbowReplay:
         """Append a MergeVecEnv rollout (the dict rollout_rainbow returns): every transition (:673). With
         autoreset the obs row of a finished env is already the reset observation, so the terminal one comes
         from final_observation."""
-        if traj.get("final_observation") is None:
-            raise ValueError("the rollout has no final_observation: episode ends would store the reset "
-                             "observation as next_state; roll out with final_observation=True")
-        self.store(obs_first, traj["obs"], traj["a1"], traj["rew"], traj["done"], traj["final_observation"],
+        self.store(obs_first, traj["obs"], traj["a1"], traj["rew"], traj["done"], self._final_observation(traj),
                    traj.get("flags"))
 
     def push(self, state, action, reward, next_state, done):
         """replay_buffer.push (:281-288), the reference's single call, through the same kernel."""
-        torch = self._torch
-        s = torch.as_tensor([list(map(float, state))], dtype=torch.float32)
-        s2 = torch.as_tensor([[list(map(float, next_state))]], dtype=torch.float32)
-        a = torch.as_tensor([[int(action)]], dtype=torch.int8)
-        r = torch.as_tensor([[[float(reward), 0.0]]], dtype=torch.float32)
-        d = torch.as_tensor([[1 if done else 0]], dtype=torch.uint8)
-        self.store(s.to(self.device), s2.to(self.device), a.to(self.device), r.to(self.device), d.to(self.device))
+        d = self._torch.as_tensor([[1 if done else 0]], dtype=self._torch.uint8)
+        self.store(*self._single(state, action, reward, next_state), d.to(self.device))
 
     def sample_rows(self, batch_size: int = 32, seed: int = 0, draw: int = 0):
         """[B, 24] rows at mg_replay_sample's Philox slots among the rows stored so far (the reference draws
         from len(storage), :322)."""
-        torch = self._torch
-        rows = torch.empty((int(batch_size), ROW), dtype=torch.float32, device=self.device)
-        rc = self._nat.lib.mg_replay_sample(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity, ROW,
-                                            seed & 0xFFFFFFFFFFFFFFFF, draw & 0xFFFFFFFFFFFFFFFF, 1, rows.data_ptr(),
-                                            None, int(batch_size), self._stream())
-        self._nat.check(rc, "mg_replay_sample")
-        return rows
+        rows = self._torch.empty((int(batch_size), ROW), dtype=self._torch.float32, device=self.device)
+        return self._sample_into(rows, None, seed, draw, True)
 
     def sample(self, batch_size: int = 32, seed: int = 0, draw: int = 0):
         """(state [B, 10], action [B] int64, reward [B], next_state [B, 10], done [B]) -- ReplayBuffer.sample's
@@ -210,16 +171,6 @@ class RainbowReplay:
         rows = self.sample_rows(batch_size, seed, draw)
         return (rows[:, :_OBS], rows[:, _OBS].to(self._torch.int64), rows[:, _OBS + 1],
                 rows[:, _OBS + 2:2 * _OBS + 2], rows[:, 2 * _OBS + 2])
-
-    def state_dict(self):
-        return {"memory": self.memory.clone(), "counter": self._counter.clone()}
-
-    def load_state_dict(self, sd):
-        mem = self._torch.as_tensor(sd["memory"])
-        if tuple(mem.shape) != tuple(self.memory.shape):
-            raise ValueError(f"expected a {tuple(self.memory.shape)} replay memory")
-        self.memory.copy_(mem)
-        self._counter.copy_(self._torch.as_tensor(sd["counter"]))
 
 
 class _LearnerNet(RainbowNet):
@@ -249,7 +200,9 @@ class _LearnerNet(RainbowNet):
         raise RuntimeError("the learner owns this net's noise: RainbowLearner.learn() redraws it")
 
 
-class RainbowLearner:
+class RainbowLearner(LearnerBase):
+    _state_of = "a RainbowLearner"
+
     def __init__(self, net, replay, lr: float = 0.001, gamma: float = 0.99, batch_size: int = 32, seed: int = 0,
                  generator=None, device=None, betas=(0.9, 0.999), eps: float = 1e-8):
         """net: a RainbowNet, or a RainbowDQN.state_dict(); the current and the target model both start from
@@ -257,43 +210,21 @@ class RainbowLearner:
         batch_size: ranbowdqn.py:645, :569, :652. seed: the key of the minibatch draws (update u draws what
         replay.sample(batch_size, seed, draw=u) returns). generator: the torch.Generator of the noise draws
         (None: torch's global one, as the reference)."""
-        import torch
-
-        from . import _native
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("RainbowLearner needs a ROCm GPU; there is no CPU fallback")
-        self._torch, self._nat = torch, _native
+        super().__init__(replay, "replay memory", device)
+        torch, _native = self._torch, self._nat
         self.replay = replay
-        self.device = torch.device(device) if device is not None else replay.device
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self.device != replay.device:
-            raise ValueError(f"the replay memory lives on {replay.device}, the learner on {self.device}")
         sd = net.state if isinstance(net, RainbowNet) else net
-        self.batch_size = int(batch_size)
-        self.hyper = _native.DqnHyper(float(lr), float(gamma), float(betas[0]), float(betas[1]), float(eps), 1, 0)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.generator = generator
-        self.learn_step_counter = 0  # Adam's step count
-        self.draw_counter = 0        # minibatches drawn so far
         assert int(_native.lib.mg_rainbow_learner_bytes()) == 4 * LEARNER_FLOATS
         self._buf = learner_array(sd).to(self.device)
-        sbytes = int(_native.lib.mg_rainbow_learn_scratch_bytes(self.batch_size))
-        if sbytes == 0:
-            raise ValueError("batch_size must be in 1..1024")
-        self._scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=self.device)
-        self._scratch_bytes = sbytes
+        sbytes = int(_native.lib.mg_rainbow_learn_scratch_bytes(int(batch_size)))
+        self._setup(batch_size, seed, sbytes, lr, gamma, betas, eps)
         self._packed = torch.empty(int(_native.lib.mg_rainbow_packed_bytes()), dtype=torch.uint8, device=self.device)
         self.net = _LearnerNet(model_state_dict(self._buf, 0), training=True, device=self.device)
         self.net._learner = self
         self._call(0)
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
     def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None):
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         rc = self._nat.lib.mg_rainbow_learn(
             self._buf.data_ptr(), self.replay.memory.data_ptr(), self.replay._counter.data_ptr(),
             self.replay.capacity, self.batch_size, U, self.learn_step_counter, self.seed, self.draw_counter,
@@ -341,18 +272,11 @@ class RainbowLearner:
     def state_dict(self):
         """Both models with their noise, Adam's moments, the counters and the noise generator's state: a run
         resumed from it continues bit for bit."""
-        return {"learner": self._buf.clone(), "learn_step_counter": self.learn_step_counter,
-                "draw_counter": self.draw_counter, "seed": self.seed,
-                "generator": None if self.generator is None else self.generator.get_state()}
+        return dict(super().state_dict(),
+                    generator=None if self.generator is None else self.generator.get_state())
 
     def load_state_dict(self, sd):
-        buf = self._torch.as_tensor(sd["learner"])
-        if buf.numel() != self._buf.numel():
-            raise ValueError("expected the state of a RainbowLearner")
-        self._buf.copy_(buf.to(self._torch.float32).reshape(-1))
-        self.learn_step_counter = int(sd["learn_step_counter"])
-        self.draw_counter = int(sd["draw_counter"])
-        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        super().load_state_dict(sd)
         if sd.get("generator") is not None:
             if self.generator is None:
                 self.generator = self._torch.Generator()

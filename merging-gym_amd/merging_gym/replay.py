@@ -27,51 +27,28 @@ from __future__ import annotations
 import ctypes
 
 from . import _native
+from ._base import RingBase
+from ._device import ptr
 
 _OBS_DIM = 10
 ROW = 2 * _OBS_DIM + 2        # main.py:91: NUM_STATES * 2 + 2
 ROW_GOAL = 2 * _OBS_DIM + 4   # hdqn.py:158: (NUM_STATES + 1) * 2 + 2
 
 
-class ReplayRing:
+class ReplayRing(RingBase):
     def __init__(self, capacity: int = 2000, device=None, goal: bool = False):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("ReplayRing needs a ROCm GPU; there is no CPU fallback")
-        if capacity < 1:
-            raise ValueError("capacity must be >= 1")
-        self._torch = torch
-        self.capacity = int(capacity)
         self.goal = bool(goal)
-        self.row = ROW_GOAL if self.goal else ROW
         self._s0 = 1 if self.goal else 0  # column of s[0]
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.memory = torch.zeros((self.capacity, self.row), dtype=torch.float32, device=self.device)
-        self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._scratch = torch.empty(0, dtype=torch.int64, device=self.device)
+        super().__init__(capacity, ROW_GOAL if self.goal else ROW, device)
+        self._scratch = self._torch.empty(0, dtype=self._torch.int64, device=self.device)
         self._sample_bufs = {}
 
     # ------------------------------------------------------------------ helpers
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
     def _scratch_for(self, n, T):
         need = int(_native.lib.mg_replay_scratch_bytes(n, T))
         if self._scratch.numel() * 8 < need:
             self._scratch = self._torch.empty((need + 7) // 8, dtype=self._torch.int64, device=self.device)
         return self._scratch
-
-    def _f32(self, t, shape):
-        torch = self._torch
-        t = torch.as_tensor(t, device=self.device)
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            t = t.to(torch.float32).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
-        return t
 
     # ------------------------------------------------------------------ stores
     @property
@@ -145,7 +122,6 @@ class ReplayRing:
         elif skip_ego_won:
             raise ValueError("skip_ego_won needs the won_mask of the step(s) (main.py:209): roll out "
                              "with won_mask=True / MergeVecEnv(won_mask=True), or pass skip_ego_won=False")
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         tr = _native.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), ptr(a1), ptr(rew),
                                  ptr(done), ptr(won_mask) if skip_ego_won else None, ptr(goal),
                                  ptr(next_goal), ptr(reward), ptr(flags), ptr(meta_goal))
@@ -162,12 +138,8 @@ class ReplayRing:
         """Append a MergeVecEnv rollout (the dict rollout_random / rollout_qnet return). With
         autoreset the obs row of a finished env is already the reset observation, so the
         terminal one must come from final_observation (roll out with final_observation=True)."""
-        if traj.get("final_observation") is None:
-            raise ValueError("the rollout has no final_observation: episode ends would store the "
-                             "reset observation as next_state; roll out with final_observation=True")
-        self.store(obs_first, traj["obs"], traj["a1"], traj["rew"], traj["done"],
-                   traj["final_observation"], traj.get("won_mask"), skip_ego_won, goal, next_goal, reward,
-                   traj.get("flags"))
+        self.store(obs_first, traj["obs"], traj["a1"], traj["rew"], traj["done"], self._final_observation(traj),
+                   traj.get("won_mask"), skip_ego_won, goal, next_goal, reward, traj.get("flags"))
 
     def store_meta(self, traj):
         """Append Goal_DQN's rows of an h-DQN rollout (MergeVecEnv.rollout_hdqn(...,
@@ -185,36 +157,25 @@ class ReplayRing:
         """The reference's single-transition call (main.py:115-119; hdqn.py:180-184 for a goal
         ring, where state / next_state are the 11-value goal states [goal] + state), through the
         same kernels."""
-        torch = self._torch
-        if self.goal:
-            gs, gs2 = [float(x) for x in state], [float(x) for x in next_state]
-            s = torch.as_tensor([gs[1:]], dtype=torch.float32)
-            s2 = torch.as_tensor([[gs2[1:]]], dtype=torch.float32)
-            a = torch.as_tensor([[int(action)]], dtype=torch.int8)
-            r = torch.as_tensor([[[float(reward), 0.0]]], dtype=torch.float32)
-            g = torch.as_tensor([[gs[0]]], dtype=torch.float32)
-            g2 = torch.as_tensor([[gs2[0]]], dtype=torch.float32)
-            self.store(s.to(self.device), s2.to(self.device), a.to(self.device), r.to(self.device),
-                       skip_ego_won=False, goal=g.to(self.device), next_goal=g2.to(self.device))
+        if not self.goal:
+            self.store(*self._single(state, action, reward, next_state), skip_ego_won=False)
             return
-        s = torch.as_tensor([list(map(float, state))], dtype=torch.float32)
-        s2 = torch.as_tensor([[list(map(float, next_state))]], dtype=torch.float32)
-        a = torch.as_tensor([[int(action)]], dtype=torch.int8)
-        r = torch.as_tensor([[[float(reward), 0.0]]], dtype=torch.float32)
-        self.store(s.to(self.device), s2.to(self.device), a.to(self.device), r.to(self.device),
-                   skip_ego_won=False)
+        gs, gs2 = [float(x) for x in state], [float(x) for x in next_state]
+        g = self._torch.as_tensor([[gs[0]]], dtype=self._torch.float32)
+        g2 = self._torch.as_tensor([[gs2[0]]], dtype=self._torch.float32)
+        self.store(*self._single(gs[1:], action, reward, gs2[1:]), skip_ego_won=False, goal=g.to(self.device),
+                   next_goal=g2.to(self.device))
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
         """memory (copy) and memory_counter -- what DQN's memory and counter hold."""
-        return {"memory": self.memory.clone(), "counter": self._counter.clone(), "goal": self.goal}
+        return dict(super().state_dict(), goal=self.goal)
 
     def load_state_dict(self, sd):
         mem = self._torch.as_tensor(sd["memory"])
         if tuple(mem.shape) != tuple(self.memory.shape) or bool(sd.get("goal", False)) != self.goal:
             raise ValueError(f"expected a {tuple(self.memory.shape)} ring (goal={self.goal})")
-        self.memory.copy_(mem)
-        self._counter.copy_(self._torch.as_tensor(sd["counter"]))
+        super().load_state_dict(sd)
 
     # ------------------------------------------------------------------ sampling
     def sample_rows(self, batch_size: int = 128, seed: int = 0, draw: int = 0,
@@ -230,11 +191,7 @@ class ReplayRing:
                    torch.empty(B, dtype=torch.int64, device=self.device))
             self._sample_bufs[B] = buf
         rows, idx = buf
-        rc = _native.lib.mg_replay_sample(
-            self.memory.data_ptr(), self._counter.data_ptr(), self.capacity, self.row, seed & 0xFFFFFFFFFFFFFFFF,
-            draw & 0xFFFFFFFFFFFFFFFF, 1 if filled_only else 0, rows.data_ptr(), idx.data_ptr(), B,
-            self._stream())
-        _native.check(rc, "mg_replay_sample")
+        self._sample_into(rows, idx, seed, draw, filled_only)
         return (rows, idx) if return_index else rows
 
     def sample(self, batch_size: int = 128, seed: int = 0, draw: int = 0, filled_only: bool = False):

@@ -8,11 +8,12 @@ from __future__ import annotations
 import ctypes
 import functools
 import os
-import shutil
 import subprocess
 import tempfile
 
 import numpy as np
+
+from native_build import cc  # noqa: F401  (re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "dqn_learn_ref.c")
@@ -22,10 +23,6 @@ CASES = [(10, 5, 128), (10, 5, 32), (10, 5, 96), (11, 5, 128), (10, 3, 128)]
 HYPER = dict(lr=0.01, gamma=0.9, beta1=0.9, beta2=0.999, eps=1e-8)  # main.py:13-14, Adam's defaults
 
 _u64, _i64, _i32, _dbl = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
-
-
-def cc():
-    return os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
 
 
 @functools.lru_cache(maxsize=1)

@@ -4,35 +4,13 @@ tests/test_sanitizers.py builds abi_sanitize. mg_host_dqn_learn runs there on ex
 buffers for (10, 5, 96) and (11, 5, 32); the device entry points only refuse. No GPU is touched and
 nothing is loaded into Python."""
 
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import ROOT
-
-NATIVE = os.path.join(ROOT, "tests", "native")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
-           UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+from native_build import hipcc, run_sanitized_driver
 
 
-def _hipcc():
-    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not found")
 def test_learn_host_code_under_asan_ubsan(tmp_path):
-    exe = str(tmp_path / "learn_sanitize")
-    b = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                        "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address", "-Xarch_host",
-                        "-fsanitize=undefined", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                        os.path.join(ROOT, "merging-gym_amd", "csrc", "merging_hip.hip"),
-                        os.path.join(NATIVE, "learn_sanitize.cpp")], capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-2000:]
-    r = subprocess.run([exe], env=ENV, capture_output=True, text=True, timeout=300)
+    r = run_sanitized_driver("learn_sanitize", tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr[-2000:]
     assert "learn sanitizer run: 0 failures" in r.stdout

@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from native_build import hipcc, run_sanitized_driver
 
 NATIVE = os.path.join(ROOT, "tests", "native")
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
@@ -33,21 +34,8 @@ def test_oracle_under_asan_ubsan(tmp_path):
     assert "oracle sanitizer run ok" in r.stdout
 
 
-def _hipcc():
-    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not found")
 def test_library_host_code_under_asan_ubsan(tmp_path):
-    exe = str(tmp_path / "abi_sanitize")
-    b = _run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-              "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-              "-I", os.path.join(ROOT, "include"), "-o", exe,
-              os.path.join(ROOT, "merging-gym_amd", "csrc", "merging_hip.hip"), os.path.join(NATIVE, "abi_sanitize.cpp")])
-    assert b.returncode == 0, b.stderr[-2000:]
-    r = _run([exe], env=ENV)
+    r = run_sanitized_driver("abi_sanitize", tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr[-2000:]
     assert "abi sanitizer run: 0 failures" in r.stdout

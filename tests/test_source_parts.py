@@ -3,23 +3,16 @@ part per subsystem (DESIGN.md's source map). Every file under csrc/ is part of t
 is left in the translation unit itself, and every part names what it uses: it compiles on its own."""
 import glob
 import os
-import shutil
 import subprocess
 
 import pytest
 
 from conftest import ROOT
 from merging_gym import build
+from native_build import hipcc
 
 CSRC = os.path.join(ROOT, "merging-gym_amd", "csrc")
 PARTS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.h")))
-
-
-def _hipcc():
-    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
 
 
 def test_no_orphan_parts():
@@ -34,10 +27,10 @@ def test_translation_unit_holds_no_kernel():
         assert "__global__" not in f.read()
 
 
-@pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
+@pytest.mark.skipif(hipcc() is None, reason="hipcc not found")
 @pytest.mark.parametrize("part", PARTS)
 def test_part_compiles_alone(part):
-    r = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
+    r = subprocess.run([hipcc(), "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
                         "-I", os.path.join(ROOT, "include"), "-x", "hip", "-fsyntax-only", os.path.join(CSRC, part)],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
