@@ -184,14 +184,16 @@ def test_fused_hdqn_rollout_at_params(coracle):
     _fused_hdqn_rollout(coracle, 577, "none", case="A", T=16)
 
 
-def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
+def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190, first_step=None):
+    """burn: random steps before the first launch; first_step: the first launch's global step index (default: burn)
+    -- tests/test_gpu_wide_words.py runs this restatement at a 64-bit seed and step index."""
     import torch
 
     import params_cases as pc
     from merging_gym import MergeVecEnv, ReplayRing
     from merging_gym.policy import NUM_GOALS, QNet, greedy_threshold
 
-    seed, dev = 9, "cuda:0"
+    dev = "cuda:0"
     params = None if case is None else pc.CASES[case]
     rng = np.random.default_rng(21)
     mk = _net_signed if opponent.endswith("-signed") else _net
@@ -207,9 +209,9 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24):
         opp_arg = (QNet.from_state_dict(op_meta_sd, device=dev), QNet.from_state_dict(op_lower_sd, device=dev))
     thr = greedy_threshold()
     env = MergeVecEnv(n, device=dev, final_observation=True)
-    k0 = 190
+    k0 = burn if first_step is None else first_step
     if case is None:
-        for k in range(k0):
+        for k in range(burn):
             env.step_random(5, opponent_random=False, step_idx=k)
     else:
         pc.fill_native(env.params, case)
