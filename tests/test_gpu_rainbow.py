@@ -115,13 +115,14 @@ STATE = ("p1", "v1", "p2", "v2", "ret1", "ret2", "tf", "_ep_stats")
 
 
 @pytest.mark.parametrize("opponent", ["none", "self"])
-@pytest.mark.parametrize("n,case", [(577, None), (1000, None), (577, "A")])
+@pytest.mark.parametrize("n,case", [(577, None), (1000, None), (577, "A"), (17, "A"), (65, "A")])
 def test_rollout_equals_composition_restatement_and_oracle(torch, coracle, nets, n, case, opponent):
     """Two consecutive launches of T = 5 (the state carried) on a mid-episode batch. (a) The launch equals,
     with torch.equal, the same steps composed from RainbowNet.forward (rotate 0 and 3) and MergeVecEnv.step;
     (b) every action is the restatement's choice on the observation the kernel acted on; (c) the C oracle's
     step on those actions gives the flags and the fp64 state bit for bit and the observations after one fp32
-    rounding; (d) a second run from the same state gives identical outputs."""
+    rounding; (d) a second run from the same state gives identical outputs. (17, "A") and (65, "A"): below and
+    just past one wave, from case A's scattered states; two of the 17 end an episode inside the ten steps."""
     T, launches, seed = 5, 2, 11
     net = nets["default"]
     eff = R.effective_ref(R.state_dict(*NETS["default"]))
