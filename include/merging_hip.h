@@ -762,6 +762,92 @@ int mg_host_rainbow_project(const float* next_dist, const float* reward, const f
                             double gamma, float* proj, int64_t n);
 int mg_host_rainbow_log(const float* x, float* y, int64_t n);
 
+/* ---- Prioritized replay (additive to ABI 21) --------------------------------------------------------
+ * SumSegmentTree / MinSegmentTree (scripts/ranbowdqn.py:130-262) and PrioritizedReplayBuffer (:326-437) beside
+ * the rows of mg_rainbow_replay_store. The script defines the class and never instantiates it; these entries
+ * are pinned to the class itself.
+ *
+ * The tree is one caller-owned device buffer of mg_per_bytes(capacity) = 8 (4 C + 2) bytes, 16-byte aligned,
+ * C = the smallest power of two >= capacity (:345-347): fp64 sum[2 C], fp64 min[2 C] -- node 1 the root, leaf
+ * i at C + i, node 0 unused, as SegmentTree._value -- then fp64 max_priority and one pad. fp64 because the
+ * reference's nodes are Python floats and the sampled indices have to be the reference's. mg_per_init writes
+ * 0.0 (:218), +inf (:256) and 1.0 (:351). Every inner node is always written as left + right, or
+ * min(left, right), of finished children (:202-205), so the tree is a pure function of its leaves: no float
+ * atomics, the same bits for every grid.
+ *
+ *   pow       x ** y = exp(y * log x) in fp64 for a normal positive finite x, the library's own, identical bits
+ *             on host and device: fdlibm's e_log.c and e_exp.c without their special cases, every operation
+ *             rounded once, no fma. A priority p enters the tree as p ** alpha; alpha == 1 takes p itself, so
+ *             that tree equals the reference's bit for bit. Error against libm pow: DESIGN.md section 5.
+ *   store     mg_per_store = mg_rainbow_replay_store (the same arguments, the same rows), then the leaves of
+ *             the written slots := max_priority ** alpha in both trees (:353-358), then their ancestors level
+ *             by level -- the written slots are a range modulo capacity, so each level's dirty nodes are that
+ *             range shifted right; one launch per level while a level is wider than a block, then one block
+ *             with a barrier per level -- then counter += n num_steps. n num_steps > capacity: the newest
+ *             `capacity` transitions are written.
+ *   sample    len = min(counter, capacity). Draw b: u = ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53 from words x, y of
+ *             mg_replay_sample's Philox block (key seed, counter (b, draw)) -- random.random()'s construction;
+ *             mass = u * S with S = sum(0, len - 1) (:364), the leaves 0 .. len - 2 in _reduce_helper's
+ *             association, right-nested over the covering nodes, widest first (:159-172). THE NEWEST SLOT
+ *             len - 1 IS THEREFORE NEVER DRAWN, as in the reference. Then find_prefixsum_idx (:241-248): from
+ *             the root, left where sum[left] > mass, else mass -= sum[left] and right. Weight (:405-412) in
+ *             fp64: p_min = min[1] / sum[1], p = sum[C + idx] / sum[1],
+ *             w = fp32((p len) ** -beta / (p_min len) ** -beta). A buffer whose priorities were never updated
+ *             gives every weight exactly 1. With len < 2 the reference recurses out of its tree; here slot 0
+ *             with weight 1.
+ *   update    mg_per_update (:417-437): leaf idx[b] := fp64(priority[b]) ** alpha in both trees, the last b
+ *             of a repeated index winning as in the reference's loop; max_priority := max(max_priority, every
+ *             priority[b]); the ancestors rebuilt a level at a time. One block, one thread per entry. Entries
+ *             the reference's asserts reject (:432-433: priority <= 0 or NaN, idx outside 0 .. len - 1) are
+ *             left out.
+ * Accepted: 1 <= capacity <= 2^32, alpha > 0, beta > 0, 1 <= batch <= 1024, tree_bytes >= mg_per_bytes.
+ * mg_host_per_init / _store / _sample / _update: the same functions on HOST pointers, synchronously.
+ * mg_host_per_uniform: the u of draw b. mg_host_per_total: S. mg_host_per_pow: out[i] = x[i] ** y[i] as above.
+ *
+ * mg_rainbow_learn_prioritized = mg_rainbow_learn drawing from the tree: its arguments, then the tree, alpha,
+ * beta, prio_eps and the optional outputs idx_out [U, B] int64 and weight_out [U, B] fp32. Per update, on the
+ * stream, nothing synchronised -- nine launches for mg_rainbow_learn's seven:
+ *   1. sample (seed, draw = first_draw + u) -> idx[b], w[b].
+ *   2. the row kernel reads ring row idx[b]; the gradient of row b carries fp32(w[b] * fp32(1 / B)), one
+ *      rounded product, where mg_rainbow_learn's carries fp32(1 / B). loss_b stays the unweighted row loss.
+ *   3. backward, Adam, noise as mg_rainbow_learn.
+ *   4. loss_out[u] = (((0 + w_0 loss_0) + w_1 loss_1) + ...) * fp32(1 / B), each product rounded once.
+ *   5. update with priority[b] = loss_b + fp32(prio_eps), one fp32 sum.
+ * The script never uses the weights (it has no prioritized run); this is the convention of the notebooks it
+ * was taken from (loss = (loss * weights).mean(), priorities loss + 1e-5). scratch:
+ * mg_rainbow_learn_prioritized_scratch_bytes(batch). prio_eps >= 0. */
+size_t mg_per_bytes(int64_t capacity);
+int mg_per_init(void* tree, size_t tree_bytes, int64_t capacity, void* stream);
+int mg_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                 int32_t num_steps, void* tree, size_t tree_bytes, double alpha, void* stream);
+int mg_per_sample(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double beta,
+                  uint64_t seed, uint64_t draw, int32_t batch, int64_t* idx_out, float* weight_out, void* stream);
+int mg_per_update(void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double alpha,
+                  const int64_t* idx, const float* priority, int32_t batch, void* stream);
+int mg_host_per_init(void* tree, size_t tree_bytes, int64_t capacity);
+int mg_host_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                      int32_t num_steps, void* tree, size_t tree_bytes, double alpha);
+int mg_host_per_sample(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double beta,
+                       uint64_t seed, uint64_t draw, int32_t batch, int64_t* idx_out, float* weight_out);
+int mg_host_per_update(void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double alpha,
+                       const int64_t* idx, const float* priority, int32_t batch);
+double mg_host_per_uniform(uint64_t b, uint64_t draw, uint64_t seed);
+int mg_host_per_total(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double* total);
+int mg_host_per_pow(const double* x, const double* y, double* out, int64_t n);
+size_t mg_rainbow_learn_prioritized_scratch_bytes(int32_t batch);
+int mg_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
+                                 int32_t batch, int32_t num_updates, uint64_t first_update, uint64_t seed,
+                                 uint64_t first_draw, const mg_dqn_hyper* hyper, const float* noise, float* loss_out,
+                                 float* rows_out, float* proj_out, float* grads_out, void* packed_out, void* scratch,
+                                 size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha, double beta,
+                                 double prio_eps, int64_t* idx_out, float* weight_out, void* stream);
+int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
+                                      int32_t batch, int32_t num_updates, uint64_t first_update, uint64_t seed,
+                                      uint64_t first_draw, const mg_dqn_hyper* hyper, const float* noise,
+                                      float* loss_out, float* rows_out, float* proj_out, float* grads_out,
+                                      void* scratch, size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha,
+                                      double beta, double prio_eps, int64_t* idx_out, float* weight_out);
+
 #ifdef __cplusplus
 }
 #endif

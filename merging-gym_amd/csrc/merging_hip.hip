@@ -45,6 +45,7 @@
 #include "mg_learn_core.h"      // the fixed-order fp32 primitives both learners share, learn_bwd_kernel
 #include "mg_learn.h"           // DQN.learn: the minibatch update kernels, their launch order and host twin
 #include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
+#include "mg_per.h"             // prioritized replay: the sum / min trees, store, sample, update, the weighted learner
 
 extern "C" {
 
@@ -613,24 +614,8 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n) {
 // ---- Rainbow learning (scripts/ranbowdqn.py:265-323, :551-609) --------------------------------------
 int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
                             int32_t num_steps, void* stream) {
-  if (!rows || !counter || !tr) return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: NULL pointer");
-  if (capacity < 1 || capacity > (int64_t{1} << 32))
-    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: need 1 <= capacity <= 2^32");
-  if (n < 0 || num_steps < 0)
-    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: n < 0 or num_steps < 0");
-  if (tr->goal || tr->next_goal || tr->reward || tr->meta_goal)
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_rainbow_replay_store: goal, next_goal, reward and meta_goal must be NULL (Rainbow rows have none)");
+  if (int e = check_rainbow_store("mg_rainbow_replay_store", rows, counter, capacity, tr, n, num_steps)) return e;
   if (n == 0 || num_steps == 0) return 0;
-  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_rainbow_replay_store: obs_first, obs, a1 (or flags) and rew are required");
-  if (misaligned(rows, 7) || misaligned(counter, 7) || misaligned(tr->obs_first, 3) || misaligned(tr->obs, 3) ||
-      misaligned(tr->final_obs, 3) || misaligned(tr->rew, 3))
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_rainbow_replay_store: rows and counter must be 8-byte, the float buffers 4-byte aligned");
-  if (n > (static_cast<int64_t>(0x7fffffff) * kBlock) / num_steps)
-    return fail(hipErrorInvalidValue, "%s", "mg_rainbow_replay_store: n * num_steps exceeds the grid limit");
   RlStore R{};
   R.X = *tr;
   R.n = n;
@@ -710,6 +695,181 @@ int mg_host_rainbow_log(const float* x, float* y, int64_t n) {
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
   if (!x || !y) return fail(hipErrorInvalidValue, "%s", "mg_host_rainbow_log: NULL pointer");
   for (int64_t i = 0; i < n; ++i) y[i] = x[i] >= 1.17549435e-38f && x[i] < INFINITY ? rb_log(x[i]) : NAN;
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- Prioritized replay (scripts/ranbowdqn.py:130-262, :326-437) ------------------------------------
+size_t mg_per_bytes(int64_t capacity) {
+  if (capacity < 1 || capacity > (int64_t{1} << 32)) return 0;
+  return static_cast<size_t>(per_doubles(capacity)) * sizeof(double);
+}
+
+int mg_per_init(void* tree, size_t tree_bytes, int64_t capacity, void* stream) {
+  if (int e = check_per_tree("mg_per_init", tree, tree_bytes, capacity)) return e;
+  const PerTree T = per_tree(tree, capacity);
+  hipLaunchKernelGGL(per_init_kernel, dim3(grid_blocks(2 * T.C + 1)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                     T);
+  return finish_launch("mg_per_init");
+}
+
+int mg_host_per_init(void* tree, size_t tree_bytes, int64_t capacity) {
+  if (int e = check_per_tree("mg_host_per_init", tree, tree_bytes, capacity)) return e;
+  const PerTree T = per_tree(tree, capacity);
+  for (int64_t i = 0; i <= 2 * T.C; ++i) per_init_at(T, i);
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                 int32_t num_steps, void* tree, size_t tree_bytes, double alpha, void* stream) {
+  if (int e = check_rainbow_store("mg_per_store", rows, counter, capacity, tr, n, num_steps)) return e;
+  if (int e = check_per_tree("mg_per_store", tree, tree_bytes, capacity)) return e;
+  if (int e = check_per_alpha("mg_per_store", alpha)) return e;
+  if (n == 0 || num_steps == 0) return 0;
+  RlStore R{};
+  R.X = *tr;
+  R.n = n;
+  R.total = n * num_steps;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
+  launch_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha, st);
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+  return finish_launch("mg_per_store");
+}
+
+int mg_host_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                      int32_t num_steps, void* tree, size_t tree_bytes, double alpha) {
+  if (int e = check_rainbow_store("mg_host_per_store", rows, counter, capacity, tr, n, num_steps)) return e;
+  if (int e = check_per_tree("mg_host_per_store", tree, tree_bytes, capacity)) return e;
+  if (int e = check_per_alpha("mg_host_per_store", alpha)) return e;
+  g_err[0] = '\0';
+  if (n == 0 || num_steps == 0) return 0;
+  RlStore R{};
+  R.X = *tr;
+  R.n = n;
+  R.total = n * num_steps;
+  for (int64_t i = 0; i < R.total; ++i) rl_store_at(R, counter, rows, capacity, i);
+  host_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha);
+  *counter += static_cast<uint64_t>(R.total);
+  return 0;
+}
+
+int mg_per_sample(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double beta,
+                  uint64_t seed, uint64_t draw, int32_t batch, int64_t* idx_out, float* weight_out, void* stream) {
+  if (int e = check_per_sample("mg_per_sample", tree, tree_bytes, counter, capacity, beta, batch, idx_out, weight_out))
+    return e;
+  const PerSample P{per_tree(const_cast<void*>(tree), capacity), counter, beta, seed, draw, batch, idx_out, nullptr,
+                    weight_out, nullptr};
+  hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(batch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), P);
+  return finish_launch("mg_per_sample");
+}
+
+int mg_host_per_sample(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double beta,
+                       uint64_t seed, uint64_t draw, int32_t batch, int64_t* idx_out, float* weight_out) {
+  if (int e = check_per_sample("mg_host_per_sample", tree, tree_bytes, counter, capacity, beta, batch, idx_out,
+                               weight_out))
+    return e;
+  const PerSample P{per_tree(const_cast<void*>(tree), capacity), counter, beta, seed, draw, batch, idx_out, nullptr,
+                    weight_out, nullptr};
+  for (int b = 0; b < batch; ++b) per_sample_at(P, b);
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_per_update(void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double alpha,
+                  const int64_t* idx, const float* priority, int32_t batch, void* stream) {
+  if (int e = check_per_update("mg_per_update", tree, tree_bytes, counter, capacity, alpha, idx, priority, batch))
+    return e;
+  const PerUpdate U{per_tree(tree, capacity), counter, alpha, idx, priority, 0.0f, 0, batch};
+  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(kPerTail), 0, static_cast<hipStream_t>(stream), U);
+  return finish_launch("mg_per_update");
+}
+
+int mg_host_per_update(void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double alpha,
+                       const int64_t* idx, const float* priority, int32_t batch) {
+  if (int e = check_per_update("mg_host_per_update", tree, tree_bytes, counter, capacity, alpha, idx, priority, batch))
+    return e;
+  host_per_update(PerUpdate{per_tree(tree, capacity), counter, alpha, idx, priority, 0.0f, 0, batch});
+  g_err[0] = '\0';
+  return 0;
+}
+
+double mg_host_per_uniform(uint64_t b, uint64_t draw, uint64_t seed) { return per_uniform(b, draw, seed); }
+
+int mg_host_per_total(const void* tree, size_t tree_bytes, const uint64_t* counter, int64_t capacity, double* total) {
+  if (!counter || !total) return fail(hipErrorInvalidValue, "%s: NULL pointer", "mg_host_per_total");
+  if (int e = check_per_tree("mg_host_per_total", tree, tree_bytes, capacity)) return e;
+  const int64_t len = per_len(counter, capacity);
+  *total = len >= 2 ? per_total(per_tree(const_cast<void*>(tree), capacity), len) : 0.0;
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_host_per_pow(const double* x, const double* y, double* out, int64_t n) {
+  if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
+  if (!x || !y || !out) return fail(hipErrorInvalidValue, "%s: NULL pointer", "mg_host_per_pow");
+  for (int64_t i = 0; i < n; ++i) out[i] = per_pow(x[i], y[i]);
+  g_err[0] = '\0';
+  return 0;
+}
+
+size_t mg_rainbow_learn_prioritized_scratch_bytes(int32_t batch) {
+  if (batch < 1 || batch > 1024) return 0;
+  return static_cast<size_t>(per_scratch(batch).total) * sizeof(float);
+}
+
+int mg_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
+                                 int32_t batch, int32_t num_updates, uint64_t first_update, uint64_t seed,
+                                 uint64_t first_draw, const mg_dqn_hyper* hyper, const float* noise, float* loss_out,
+                                 float* rows_out, float* proj_out, float* grads_out, void* packed_out, void* scratch,
+                                 size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha, double beta,
+                                 double prio_eps, int64_t* idx_out, float* weight_out, void* stream) {
+  const char* what = "mg_rainbow_learn_prioritized";
+  if (int e = check_rainbow_learn(what, learner, rows, counter, capacity, batch, num_updates, hyper, noise, loss_out,
+                                  rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes))
+    return e;
+  if (int e = check_per_learn(what, tree, tree_bytes, capacity, alpha, beta, prio_eps, idx_out, weight_out, batch,
+                              scratch_bytes))
+    return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
+  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 0);
+  PerLearn Q = make_per_learn(L, tree, alpha, beta, prio_eps, idx_out, weight_out, scratch);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
+                             noise, loss_out, rows_out, proj_out, grads_out);
+    per_learn_set_update(Q, L, u);
+    launch_per_learn_update(Q, L, st);
+  }
+  if (packed_out)
+    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st,
+                       rainbow_learn_tensors(learner, L.eff), static_cast<uint8_t*>(packed_out));
+  return finish_launch(what);
+}
+
+int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
+                                      int32_t batch, int32_t num_updates, uint64_t first_update, uint64_t seed,
+                                      uint64_t first_draw, const mg_dqn_hyper* hyper, const float* noise,
+                                      float* loss_out, float* rows_out, float* proj_out, float* grads_out,
+                                      void* scratch, size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha,
+                                      double beta, double prio_eps, int64_t* idx_out, float* weight_out) {
+  const char* what = "mg_host_rainbow_learn_prioritized";
+  if (int e = check_rainbow_learn(what, learner, rows, counter, capacity, batch, num_updates, hyper, noise, loss_out,
+                                  rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes))
+    return e;
+  if (int e = check_per_learn(what, tree, tree_bytes, capacity, alpha, beta, prio_eps, idx_out, weight_out, batch,
+                              scratch_bytes))
+    return e;
+  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
+  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
+  PerLearn Q = make_per_learn(L, tree, alpha, beta, prio_eps, idx_out, weight_out, scratch);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
+                             noise, loss_out, rows_out, proj_out, grads_out);
+    per_learn_set_update(Q, L, u);
+    host_per_learn_update(Q, L);
+  }
   g_err[0] = '\0';
   return 0;
 }

@@ -37,14 +37,14 @@ inline LearnAdam learn_adam_scalars(const mg_dqn_hyper* h, uint64_t t) {
 }
 
 // ---------------------------------------------------------------------------- per-element functions
-// Slot of minibatch row b: mg_replay_sample's draw (replay_sample_kernel), word x of
-// Philox4x32-10(key = seed, counter = (b, draw)) scaled to [0, m).
-MG_HD uint64_t learn_slot(uint64_t b, uint64_t draw, uint64_t seed, uint64_t m) {
+// Words x, y of Philox4x32-10(key = seed, counter = (b, draw)): the block every minibatch draw of row b takes
+// its bits from.
+MG_HD void learn_words(uint64_t b, uint64_t draw, uint64_t seed, uint32_t& w0, uint32_t& w1) {
 #ifdef __HIP_DEVICE_COMPILE__
   const uint4 u = philox4x32_10(make_uint4(static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32),
                                            static_cast<uint32_t>(draw), static_cast<uint32_t>(draw >> 32)),
                                 static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-  return (static_cast<uint64_t>(u.x) * m) >> 32;
+  w0 = u.x, w1 = u.y;
 #else
   uint32_t c0 = static_cast<uint32_t>(b), c1 = static_cast<uint32_t>(b >> 32);
   uint32_t c2 = static_cast<uint32_t>(draw), c3 = static_cast<uint32_t>(draw >> 32);
@@ -61,8 +61,16 @@ MG_HD uint64_t learn_slot(uint64_t b, uint64_t draw, uint64_t seed, uint64_t m) 
     c0 = n0;
     c2 = n2;
   }
-  return (static_cast<uint64_t>(c0) * m) >> 32;
+  w0 = c0, w1 = c1;
 #endif
+}
+
+// Slot of minibatch row b: mg_replay_sample's draw (replay_sample_kernel), word x of that block scaled to
+// [0, m).
+MG_HD uint64_t learn_slot(uint64_t b, uint64_t draw, uint64_t seed, uint64_t m) {
+  uint32_t w0, w1;
+  learn_words(b, draw, seed, w0, w1);
+  return (static_cast<uint64_t>(w0) * m) >> 32;
 }
 
 // Rows the draw chooses among: the capacity, or with filled_only the rows stored so far (>= 1).
@@ -120,6 +128,13 @@ MG_HD float learn_sum(const float* a, int64_t sa, int n) {
     for (int u = 0; u < kLBatch; ++u) acc = acc + av[u];
   }
   for (; i < n; ++i) acc = acc + a[i * sa];
+  return acc;
+}
+
+// Sequential sum over i ascending of w[i] a[i], each product rounded once, from +0 (the weighted loss).
+MG_HD float learn_wsum(const float* w, const float* a, int n) {
+  float acc = 0.0f;
+  for (int i = 0; i < n; ++i) acc = acc + w[i] * a[i];
   return acc;
 }
 

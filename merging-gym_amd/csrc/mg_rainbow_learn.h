@@ -25,9 +25,8 @@ struct RlStore {
   int64_t total;  // T n
 };
 
-__global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const uint64_t* counter, float* rows,
-                                                          int64_t cap) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+// transition idx = t n + i of a store (the host twin of the prioritized store runs it too)
+MG_HD void rl_store_at(const RlStore& R, const uint64_t* counter, float* rows, int64_t cap, int64_t idx) {
   // only the newest `cap` transitions survive sequential pushes: they occupy distinct slots
   const int64_t skip = R.total > cap ? R.total - cap : 0;
   if (idx >= R.total || idx < skip) return;
@@ -46,6 +45,11 @@ __global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const
   f32x2* d = reinterpret_cast<f32x2*>(rows + slot * kRlRow);
 #pragma unroll
   for (int k = 0; k < kRlRow / 2; ++k) d[k] = f32x2{v[2 * k], v[2 * k + 1]};
+}
+
+__global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const uint64_t* counter, float* rows,
+                                                          int64_t cap) {
+  rl_store_at(R, counter, rows, cap, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
 }
 
 // ============================================================================ compute_td_loss
@@ -116,7 +120,16 @@ struct RLearn {
   float *rows_out, *loss_out, *proj_out, *grads_out;  // this update's, or NULL
   float gamma, inv_b;
   LearnAdam A;
+  // prioritized replay (mg_per.h), or NULL: row b is ring row pidx[b] and its loss is weighted by pw[b]
+  const int64_t* pidx;
+  const float* pw;
 };
+
+// the ring row of minibatch row b, and the factor its gradient carries: 1 / B, or w_b * (1 / B) rounded once
+MG_HD uint64_t rl_row_slot(const RLearn& L, uint64_t live, int b) {
+  return L.pidx ? static_cast<uint64_t>(L.pidx[b]) : learn_slot(static_cast<uint64_t>(b), L.draw, L.seed, live);
+}
+MG_HD float rl_row_scale(const RLearn& L, int b) { return L.pw ? L.pw[b] * L.inv_b : L.inv_b; }
 
 // ---------------------------------------------------------------------------- per-element functions
 // log(x) for a normal x > 0, the same bits on host and device (the loss takes it on [0.01, 0.99]): x = 2^k m
@@ -270,10 +283,11 @@ MG_HD float rl_param_grad(const RLearn& L, int i) {
   return L.geff[N.e + nw + r - N.out] * eps[N.e + nw + r - N.out];
 }
 
-// item i of the Adam launch: parameter i, or at i == kRlParams the loss, the sequential sum of loss_b times 1 / B
+// item i of the Adam launch: parameter i, or at i == kRlParams the loss, the sequential sum of loss_b (with
+// weights: of w_b * loss_b, each product rounded once) times 1 / B
 MG_HD void rl_adam_at(const RLearn& L, int i) {
   if (i == kRlParams) {
-    if (L.loss_out) *L.loss_out = learn_sum(L.lossb, 1, L.B) * L.inv_b;
+    if (L.loss_out) *L.loss_out = (L.pw ? learn_wsum(L.pw, L.lossb, L.B) : learn_sum(L.lossb, 1, L.B)) * L.inv_b;
     return;
   }
   const float g = rl_param_grad(L, i);
@@ -324,7 +338,7 @@ MG_HD LearnBwd rl_bwd_layer(const RLearn& L, int which) {
 // Row b's part of an update on plain memory -- both forwards, the projection, loss_b and dlogits -- which the
 // host twin runs as it stands; rl_forward_kernel gives the same steps one thread per unit.
 inline void host_rl_forward_row(const RLearn& L, uint64_t live, int b) {
-  const float* row = L.ring + learn_slot(static_cast<uint64_t>(b), L.draw, L.seed, live) * kRlRow;
+  const float* row = L.ring + rl_row_slot(L, live, b) * kRlRow;
   const float* z = L.buf + kRlOffZ;
   float h1[kRbH1], h2[kRbH2], hv[kRbHS], ha[kRbHS], lg[kRbLogits], p[kRbActions * kRbAtoms], q[kRbActions];
   float bb[kRbAtoms], proj[kRbAtoms], dx[kRbAtoms];
@@ -355,7 +369,7 @@ inline void host_rl_forward_row(const RLearn& L, uint64_t live, int b) {
       }
     } else {
       const int astar = learn_action(row[kRlColA], kRbActions);
-      L.lossb[b] = rl_loss_row(p + astar * kRbAtoms, proj, L.inv_b, dx);
+      L.lossb[b] = rl_loss_row(p + astar * kRbAtoms, proj, rl_row_scale(L, b), dx);
       for (int t = 0; t < kRbLogits; ++t) L.dlog[b * kRbLogits + t] = rl_dlogit(dx, astar, t);
       for (int j = 0; j < kRbH1; ++j) L.h1[b * kRbH1 + j] = h1[j];
       for (int j = 0; j < kRbH2; ++j) L.h2[b * kRbH2 + j] = h2[j];
@@ -376,7 +390,7 @@ __global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const RLearn
   const float* z = L.buf + kRlOffZ;
   if (threadIdx.x < kRlRow) {
     const uint64_t live = learn_rows_live(L.cap, L.counter, 1);
-    const float v = L.ring[learn_slot(static_cast<uint64_t>(b), L.draw, L.seed, live) * kRlRow + threadIdx.x];
+    const float v = L.ring[rl_row_slot(L, live, b) * kRlRow + threadIdx.x];
     srow[threadIdx.x] = v;
     L.rows[b * kRlRow + threadIdx.x] = v;
     if (L.rows_out) L.rows_out[b * kRlRow + threadIdx.x] = v;
@@ -427,7 +441,7 @@ __global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const RLearn
   }
   __syncthreads();
   const int astar = learn_action(srow[kRlColA], kRbActions);
-  if (!pass && t == 0) L.lossb[b] = rl_loss_row(p[0] + astar * kRbAtoms, proj, L.inv_b, dx);
+  if (!pass && t == 0) L.lossb[b] = rl_loss_row(p[0] + astar * kRbAtoms, proj, rl_row_scale(L, b), dx);
   __syncthreads();
   if (!pass && t < kRbLogits) L.dlog[b * kRbLogits + t] = rl_dlogit(dx, astar, t);
 }
@@ -467,6 +481,28 @@ __global__ __launch_bounds__(kBlock) void rl_noise_eff_kernel(const RLearn L, in
 }
 
 // ---------------------------------------------------------------------------- host side of a call
+// What mg_rainbow_replay_store and the prioritized stores refuse (n == 0 or num_steps == 0 is a no-op the caller
+// returns from before the required arrays are looked at).
+int check_rainbow_store(const char* what, const float* rows, const uint64_t* counter, int64_t capacity,
+                        const mg_transitions* tr, int64_t n, int32_t num_steps) {
+  if (!rows || !counter || !tr) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (capacity < 1 || capacity > (int64_t{1} << 32))
+    return fail(hipErrorInvalidValue, "%s: need 1 <= capacity <= 2^32", what);
+  if (n < 0 || num_steps < 0) return fail(hipErrorInvalidValue, "%s: n < 0 or num_steps < 0", what);
+  if (tr->goal || tr->next_goal || tr->reward || tr->meta_goal)
+    return fail(hipErrorInvalidValue,
+                "%s: goal, next_goal, reward and meta_goal must be NULL (Rainbow rows have none)", what);
+  if (n == 0 || num_steps == 0) return 0;
+  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
+    return fail(hipErrorInvalidValue, "%s: obs_first, obs, a1 (or flags) and rew are required", what);
+  if (misaligned(rows, 7) || misaligned(counter, 7) || misaligned(tr->obs_first, 3) || misaligned(tr->obs, 3) ||
+      misaligned(tr->final_obs, 3) || misaligned(tr->rew, 3))
+    return fail(hipErrorInvalidValue, "%s: rows and counter must be 8-byte, the float buffers 4-byte aligned", what);
+  if (n > (static_cast<int64_t>(0x7fffffff) * kBlock) / num_steps)
+    return fail(hipErrorInvalidValue, "%s: n * num_steps exceeds the grid limit", what);
+  return 0;
+}
+
 // What mg_rainbow_learn and mg_host_rainbow_learn refuse, before anything is read or launched.
 int check_rainbow_learn(const char* what, const float* learner, const float* rows, const uint64_t* counter,
                         int64_t capacity, int32_t batch, int32_t num_updates, const mg_dqn_hyper* hyper,

@@ -24,7 +24,7 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .rainbow import RainbowNet
 
         return RainbowNet
-    if name in ("RainbowReplay", "RainbowLearner"):
+    if name in ("RainbowReplay", "RainbowLearner", "PrioritizedRainbowReplay", "PrioritizedRainbowLearner"):
         from . import rainbow_learn
 
         return getattr(rainbow_learn, name)

@@ -198,6 +198,33 @@ def _load(path=LIB_PATH):
     for f in (lib.mg_rainbow_replay_store, lib.mg_rainbow_learn, lib.mg_host_rainbow_learn,
               lib.mg_host_rainbow_project, lib.mg_host_rainbow_log):
         f.restype = _c.c_int
+    # Prioritized replay (additive to ABI 21): the sum / min trees, store, sample, update, the weighted learner
+    lib.mg_per_bytes.argtypes = [_c.c_int64]
+    lib.mg_per_bytes.restype = _c.c_size_t
+    lib.mg_per_init.argtypes = [_P, _c.c_size_t, _c.c_int64, _P]
+    lib.mg_host_per_init.argtypes = [_P, _c.c_size_t, _c.c_int64]
+    per_store = [_P, _P, _c.c_int64, _c.POINTER(Transitions), _c.c_int64, _c.c_int32, _P, _c.c_size_t, _c.c_double]
+    lib.mg_per_store.argtypes = per_store + [_P]
+    lib.mg_host_per_store.argtypes = per_store
+    per_sample = [_P, _c.c_size_t, _P, _c.c_int64, _c.c_double, _c.c_uint64, _c.c_uint64, _c.c_int32, _P, _P]
+    lib.mg_per_sample.argtypes = per_sample + [_P]
+    lib.mg_host_per_sample.argtypes = per_sample
+    per_update = [_P, _c.c_size_t, _P, _c.c_int64, _c.c_double, _P, _P, _c.c_int32]
+    lib.mg_per_update.argtypes = per_update + [_P]
+    lib.mg_host_per_update.argtypes = per_update
+    lib.mg_host_per_uniform.argtypes = [_c.c_uint64] * 3
+    lib.mg_host_per_uniform.restype = _c.c_double
+    lib.mg_host_per_total.argtypes = [_P, _c.c_size_t, _P, _c.c_int64, _P]
+    lib.mg_host_per_pow.argtypes = [_P, _P, _P, _c.c_int64]
+    lib.mg_rainbow_learn_prioritized_scratch_bytes.argtypes = [_c.c_int32]
+    lib.mg_rainbow_learn_prioritized_scratch_bytes.restype = _c.c_size_t
+    per_learn = [_P, _c.c_size_t, _c.c_double, _c.c_double, _c.c_double, _P, _P]
+    lib.mg_rainbow_learn_prioritized.argtypes = rl_args + [_P, _P, _c.c_size_t] + per_learn + [_P]
+    lib.mg_host_rainbow_learn_prioritized.argtypes = rl_args + [_P, _c.c_size_t] + per_learn
+    for f in (lib.mg_per_init, lib.mg_host_per_init, lib.mg_per_store, lib.mg_host_per_store, lib.mg_per_sample,
+              lib.mg_host_per_sample, lib.mg_per_update, lib.mg_host_per_update, lib.mg_host_per_total,
+              lib.mg_host_per_pow, lib.mg_rainbow_learn_prioritized, lib.mg_host_rainbow_learn_prioritized):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

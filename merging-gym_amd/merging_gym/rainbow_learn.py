@@ -19,6 +19,16 @@ the loop of ranbowdqn.py:662-691 closes without leaving the device:
 The arithmetic is fp32 in the fixed order include/merging_hip.h documents, so a run is reproducible bit for
 bit, also across a state_dict() / load_state_dict() resume. The noise is torch's: every update consumes the
 draws of two RainbowNet.reset_noise calls (the current model's, then the target's) from `generator`.
+
+PrioritizedRainbowReplay and PrioritizedRainbowLearner are the same pair over the script's
+PrioritizedReplayBuffer (:326-437) and its sum / min segment trees (:130-262), which the script defines and
+never runs: transitions enter with max_priority ** alpha, every update draws its minibatch from the tree,
+weights the rows' losses and writes their new priorities back (nine launches, mg_rainbow_learn_prioritized):
+
+    replay = PrioritizedRainbowReplay(10000, alpha=0.6, device="cuda:0")
+    learner = PrioritizedRainbowLearner(sd, replay, beta=0.4, prio_eps=1e-5)
+    replay.store_rollout(obs0, traj)
+    learner.learn(4, beta=0.5)                             # beta per call: an annealing schedule
 """
 
 from __future__ import annotations
@@ -26,7 +36,7 @@ from __future__ import annotations
 import ctypes
 
 from ._base import LearnerBase, RingBase
-from ._device import ptr
+from ._device import U64, ptr
 from .rainbow import NOISY, NUM_ATOMS, PLAIN, SHAPES, RainbowNet
 
 ROW = 24  # [s(10), a, r, s'(10), done, 0]: 8-byte aligned rows mg_replay_sample copies as they are
@@ -142,10 +152,13 @@ class RainbowReplay(RingBase):
             final_obs = self._f32(final_obs, (T, n, _OBS))
         tr = self._nat.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), ptr(a1), ptr(rew), ptr(done), None,
                                    None, None, None, ptr(flags), None)
+        self._store_call(tr, n, T)
+        self._keepalive = (obs_first, obs, a1, rew, done, final_obs, flags)
+
+    def _store_call(self, tr, n, T):
         rc = self._nat.lib.mg_rainbow_replay_store(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity,
                                                    ctypes.byref(tr), n, T, self._stream())
         self._nat.check(rc, "mg_rainbow_replay_store")
-        self._keepalive = (obs_first, obs, a1, rew, done, final_obs, flags)
 
     def store_rollout(self, obs_first, traj):
         """Append a MergeVecEnv rollout (the dict rollout_rainbow returns): every transition (:673). With
@@ -171,6 +184,91 @@ class RainbowReplay(RingBase):
         rows = self.sample_rows(batch_size, seed, draw)
         return (rows[:, :_OBS], rows[:, _OBS].to(self._torch.int64), rows[:, _OBS + 1],
                 rows[:, _OBS + 2:2 * _OBS + 2], rows[:, 2 * _OBS + 2])
+
+
+class PrioritizedRainbowReplay(RainbowReplay):
+    """PrioritizedReplayBuffer(capacity, alpha) (:326-437): RainbowReplay's rows with the sum and min segment
+    trees (:130-262) beside them, one fp64 device buffer (include/merging_hip.h, mg_per_bytes). A stored
+    transition enters with max_priority ** alpha (:353-358); store, sample and update_priorities are
+    stream-ordered launches and nothing is synchronised. The script defines the class and never builds one;
+    this twin is pinned to the class itself."""
+
+    def __init__(self, capacity: int = 10000, alpha: float = 0.6, device=None):
+        super().__init__(capacity, device)
+        if not alpha > 0:
+            raise ValueError("alpha must be > 0")  # :342
+        torch, lib = self._torch, self._nat.lib
+        self.alpha = float(alpha)
+        self._tree_bytes = int(lib.mg_per_bytes(self.capacity))
+        self._tree = torch.empty(self._tree_bytes // 8, dtype=torch.float64, device=self.device)
+        self._nat.check(lib.mg_per_init(self._tree.data_ptr(), self._tree_bytes, self.capacity, self._stream()),
+                        "mg_per_init")
+
+    def _store_call(self, tr, n, T):
+        rc = self._nat.lib.mg_per_store(self.memory.data_ptr(), self._counter.data_ptr(), self.capacity,
+                                        ctypes.byref(tr), n, T, self._tree.data_ptr(), self._tree_bytes, self.alpha,
+                                        self._stream())
+        self._nat.check(rc, "mg_per_store")
+
+    def sample_indices(self, batch_size: int = 32, beta: float = 0.4, seed: int = 0, draw: int = 0):
+        """(idxes [B] int64, weights [B] fp32) of _sample_proportional (:360-367) and the importance weights
+        (:405-412), on the device; draw b takes its uniform from mg_replay_sample's Philox block (seed, draw).
+        The prefix the reference draws from ends one slot short (sum(0, len - 1), :364), so the newest slot
+        len - 1 is never drawn; this twin keeps that. Nothing is synchronised; fewer than two stored
+        transitions give slot 0 with weight 1 (sample() refuses them)."""
+        torch = self._torch
+        idx = torch.empty(int(batch_size), dtype=torch.int64, device=self.device)
+        w = torch.empty(int(batch_size), dtype=torch.float32, device=self.device)
+        rc = self._nat.lib.mg_per_sample(self._tree.data_ptr(), self._tree_bytes, self._counter.data_ptr(),
+                                         self.capacity, float(beta), seed & U64, draw & U64, int(batch_size),
+                                         idx.data_ptr(), w.data_ptr(), self._stream())
+        self._nat.check(rc, "mg_per_sample")
+        return idx, w
+
+    def sample(self, batch_size: int = 32, beta: float = 0.4, seed: int = 0, draw: int = 0):
+        """(state, action, reward, next_state, done, weights [B] fp32, idxes [B] int64) --
+        PrioritizedReplayBuffer.sample (:369-415). The newest slot is never drawn, as in the reference (see
+        sample_indices). With fewer than two stored transitions the reference recurses out of its tree; this
+        raises ValueError after reading the length, which synchronises."""
+        if not beta > 0:
+            raise ValueError("beta must be > 0")  # :401
+        if len(self) < 2:
+            raise ValueError("PrioritizedRainbowReplay.sample needs at least two stored transitions")
+        idx, w = self.sample_indices(batch_size, beta, seed, draw)
+        rows = self.memory[idx]
+        return (rows[:, :_OBS], rows[:, _OBS].to(self._torch.int64), rows[:, _OBS + 1],
+                rows[:, _OBS + 2:2 * _OBS + 2], rows[:, 2 * _OBS + 2], w, idx)
+
+    def update_priorities(self, idxes, priorities):
+        """update_priorities (:417-437): leaf idxes[b] := priorities[b] ** alpha, the last of a repeated index
+        winning; max_priority takes every priority. Up to 1024 entries per call; an entry the reference's
+        asserts reject (priority <= 0, an index outside the stored slots) is left out."""
+        torch = self._torch
+        idx = torch.as_tensor(idxes, device=self.device).to(torch.int64).contiguous().reshape(-1)
+        pr = torch.as_tensor(priorities, device=self.device).to(torch.float32).contiguous().reshape(-1)
+        if idx.numel() != pr.numel():
+            raise ValueError("idxes and priorities must have the same length")  # :430
+        rc = self._nat.lib.mg_per_update(self._tree.data_ptr(), self._tree_bytes, self._counter.data_ptr(),
+                                         self.capacity, self.alpha, idx.data_ptr(), pr.data_ptr(), idx.numel(),
+                                         self._stream())
+        self._nat.check(rc, "mg_per_update")
+        self._keepalive_update = (idx, pr)
+
+    @property
+    def max_priority(self):
+        """_max_priority (:351, :437). Synchronises."""
+        return float(self._tree[-2].item())
+
+    def state_dict(self):
+        return dict(super().state_dict(), tree=self._tree.clone(), alpha=self.alpha)
+
+    def load_state_dict(self, sd):
+        tree = self._torch.as_tensor(sd["tree"])
+        if tree.numel() != self._tree.numel():
+            raise ValueError(f"expected a tree of {self._tree.numel()} doubles")
+        super().load_state_dict(sd)
+        self._tree.copy_(tree.to(self._torch.float64).reshape(-1))
+        self.alpha = float(sd["alpha"])
 
 
 class _LearnerNet(RainbowNet):
@@ -202,6 +300,7 @@ class _LearnerNet(RainbowNet):
 
 class RainbowLearner(LearnerBase):
     _state_of = "a RainbowLearner"
+    _entry, _prioritized = "mg_rainbow_learn", False
 
     def __init__(self, net, replay, lr: float = 0.001, gamma: float = 0.99, batch_size: int = 32, seed: int = 0,
                  generator=None, device=None, betas=(0.9, 0.999), eps: float = 1e-8):
@@ -209,7 +308,8 @@ class RainbowLearner(LearnerBase):
         it, noise included (update_target, :648). replay: the RainbowReplay learn() draws from. lr, gamma,
         batch_size: ranbowdqn.py:645, :569, :652. seed: the key of the minibatch draws (update u draws what
         replay.sample(batch_size, seed, draw=u) returns). generator: the torch.Generator of the noise draws
-        (None: torch's global one, as the reference)."""
+        (None: torch's global one, as the reference). A PrioritizedRainbowReplay takes the subclass
+        PrioritizedRainbowLearner."""
         super().__init__(replay, "replay memory", device)
         torch, _native = self._torch, self._nat
         self.replay = replay
@@ -217,21 +317,29 @@ class RainbowLearner(LearnerBase):
         self.generator = generator
         assert int(_native.lib.mg_rainbow_learner_bytes()) == 4 * LEARNER_FLOATS
         self._buf = learner_array(sd).to(self.device)
-        sbytes = int(_native.lib.mg_rainbow_learn_scratch_bytes(int(batch_size)))
+        if isinstance(replay, PrioritizedRainbowReplay) != self._prioritized:
+            raise ValueError("a PrioritizedRainbowReplay takes a PrioritizedRainbowLearner, a RainbowReplay a "
+                             "RainbowLearner")
+        sbytes = int(getattr(_native.lib, self._entry + "_scratch_bytes")(int(batch_size)))
         self._setup(batch_size, seed, sbytes, lr, gamma, betas, eps)
         self._packed = torch.empty(int(_native.lib.mg_rainbow_packed_bytes()), dtype=torch.uint8, device=self.device)
         self.net = _LearnerNet(model_state_dict(self._buf, 0), training=True, device=self.device)
         self.net._learner = self
         self._call(0)
 
-    def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None):
-        rc = self._nat.lib.mg_rainbow_learn(
+    def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None, extra=()):
+        """One call of the library's learner; extra: what the prioritized entry point takes behind the scratch."""
+        rc = getattr(self._nat.lib, self._entry)(
             self._buf.data_ptr(), self.replay.memory.data_ptr(), self.replay._counter.data_ptr(),
             self.replay.capacity, self.batch_size, U, self.learn_step_counter, self.seed, self.draw_counter,
             ctypes.byref(self.hyper), ptr(noise), ptr(loss), ptr(rows), ptr(proj), ptr(grads),
-            self._packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes, self._stream())
-        self._nat.check(rc, "mg_rainbow_learn")
+            self._packed.data_ptr(), self._scratch.data_ptr(), self._scratch_bytes, *(extra or self._extra()),
+            self._stream())
+        self._nat.check(rc, self._entry)
         self.net._stale = True
+
+    def _extra(self):
+        return ()
 
     def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
               return_proj: bool = False, return_grads: bool = False):
@@ -239,6 +347,10 @@ class RainbowLearner(LearnerBase):
         acting net repacked; nothing is synchronised. Returns None, the one requested device tensor, or a
         tuple of the requested ones in the order loss [U], rows [U, B, 24], proj [U, B, 51], grads [U, P]
         (the gradients in named_parameters() order)."""
+        return self._learn(num_updates, return_loss, return_rows, return_proj, return_grads)
+
+    def _learn(self, num_updates, return_loss, return_rows, return_proj, return_grads, more=(), extra=()):
+        """more: further optional output tensors, returned behind the four; extra: see _call."""
         torch = self._torch
         U = int(num_updates)
         if U < 0:
@@ -249,11 +361,11 @@ class RainbowLearner(LearnerBase):
         proj, grads = new(return_proj, U, B, NUM_ATOMS), new(return_grads, U, NUM_PARAMS)
         if U > 0:
             noise = noise_factors(U, self.generator).to(self.device)
-            self._call(U, noise, loss, rows, proj, grads)
+            self._call(U, noise, loss, rows, proj, grads, extra)
             self._keepalive = noise
             self.learn_step_counter += U
             self.draw_counter += U
-        out = tuple(t for t in (loss, rows, proj, grads) if t is not None)
+        out = tuple(t for t in (loss, rows, proj, grads, *more) if t is not None)
         return None if not out else out[0] if len(out) == 1 else out
 
     def sync_target(self):
@@ -282,3 +394,47 @@ class RainbowLearner(LearnerBase):
                 self.generator = self._torch.Generator()
             self.generator.set_state(sd["generator"])
         self._call(0)
+
+
+class PrioritizedRainbowLearner(RainbowLearner):
+    """RainbowLearner on a PrioritizedRainbowReplay (libmerging_hip.so's mg_rainbow_learn_prioritized): every
+    update draws its minibatch from the tree (the draw of replay.sample_indices(batch_size, beta, seed, draw=u)),
+    multiplies each row's loss by its importance weight -- loss = (loss_b * weights).mean() -- and writes
+    loss_b + prio_eps back as the rows' priorities: nine launches per update, the sample before and the priority
+    update behind RainbowLearner's seven, nothing synchronised. The script defines PrioritizedReplayBuffer and
+    never runs it, so this use of it is the convention of the notebooks the script was taken from, not the
+    script's. A row whose loss_b + prio_eps is not positive (Rainbow's loss can be negative: the gathered target
+    row stays support-scaled) keeps its priority, as update_priorities' assert would refuse it."""
+
+    _state_of = "a PrioritizedRainbowLearner"
+    _entry, _prioritized = "mg_rainbow_learn_prioritized", True
+
+    def __init__(self, net, replay, lr: float = 0.001, gamma: float = 0.99, batch_size: int = 32, seed: int = 0,
+                 generator=None, device=None, betas=(0.9, 0.999), eps: float = 1e-8, beta: float = 0.4,
+                 prio_eps: float = 1e-5):
+        """RainbowLearner's arguments, then beta: the importance weights' exponent (learn() may override it per
+        call), prio_eps: added to a row's loss to give its new priority."""
+        if not (beta > 0 and prio_eps >= 0):
+            raise ValueError("beta must be > 0 and prio_eps >= 0")
+        self.beta, self.prio_eps = float(beta), float(prio_eps)
+        super().__init__(net, replay, lr, gamma, batch_size, seed, generator, device, betas, eps)
+
+    def _extra(self, beta=None, idx=None, weights=None):
+        r = self.replay
+        return (r._tree.data_ptr(), r._tree_bytes, r.alpha, self.beta if beta is None else float(beta), self.prio_eps,
+                ptr(idx), ptr(weights))
+
+    def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
+              return_proj: bool = False, return_grads: bool = False, return_idx: bool = False,
+              return_weights: bool = False, beta=None):
+        """RainbowLearner.learn with, behind its four outputs, idx [U, B] int64 (the sampled slots) and weights
+        [U, B] fp32. beta: this call's importance exponent, for an annealing schedule (default: the
+        constructor's). loss [U] is the weighted mean; the rows' priorities are updated from the unweighted
+        row losses."""
+        if beta is not None and not beta > 0:
+            raise ValueError("beta must be > 0")
+        torch, U, B = self._torch, max(int(num_updates), 0), self.batch_size
+        idx = torch.empty((U, B), dtype=torch.int64, device=self.device) if return_idx else None
+        weights = torch.empty((U, B), dtype=torch.float32, device=self.device) if return_weights else None
+        return self._learn(num_updates, return_loss, return_rows, return_proj, return_grads, (idx, weights),
+                           self._extra(beta, idx, weights))

@@ -9,10 +9,15 @@ Per batch size (32, the reference's, and 128) in one process on one GPU:
   torch_us       ranbowdqn.py's compute_td_loss (:554-609) in eager torch on device tensors -- both forwards,
                  the projection with index_add_, the clamped cross-entropy, Adam, both reset_noise calls (drawn
                  on the host as the reference draws them) -- fed by RainbowReplay.sample, timed the same way;
+  prioritized_us the same call on a PrioritizedRainbowReplay (alpha 0.6, beta 0.4) of the same rows, whose tree 64
+                 rounds of update_priorities have shaped: nine launches per update, the sample before and the
+                 priority update behind the seven;
   launches       kernel launches per update and per_launch_us = ours_us / launches;
   kernels        per kernel, the mean device time of one launch and the launches per update, from
                  torch.profiler's kernel records of a separate pass of 20 updates. null if the profiler gave
                  no kernel records.
+"store": one store of n = 2^20 envs x T = 16 steps through mg_rainbow_replay_store (uniform_us) and through
+mg_per_store (prioritized_us: the rows, the written leaves, their ancestors level by level), per ring capacity.
 Best of `repeats` alternating runs. The replay memory holds seeded random rows and the nets their default
 initialisation: the time does not depend on the values.
 """
@@ -30,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "merging-gym_amd"))
 
 BATCHES = (32, 128)
+PER_LAUNCHES = 9  # the sample, the seven, the priority update
 LAUNCHES = 7  # rows + both forwards + projection + dlogits, four backward launches, Adam + loss, noise + effective
 
 
@@ -133,7 +139,7 @@ def kernel_breakdown(torch, learner, updates=20):
             torch.cuda.synchronize()
         rows = {}
         for ev in prof.events():
-            m = re.search(r"(rl_\w+_kernel|learn_\w+_kernel|rainbow_pack_kernel)", ev.name)
+            m = re.search(r"(rl_\w+_kernel|learn_\w+_kernel|per_\w+_kernel|rainbow_pack_kernel)", ev.name)
             if not m:
                 continue
             t = getattr(ev, "device_time", None)
@@ -150,6 +156,33 @@ def kernel_breakdown(torch, learner, updates=20):
         return {"error": repr(e)}
 
 
+def fill(torch, replay, dev):
+    n = replay.capacity
+    replay.memory.copy_(torch.rand(replay.memory.shape, device=dev) * 10.0)
+    replay.memory[:, 10] = torch.randint(0, 5, (n,), device=dev).float()
+    replay.memory[:, 22] = torch.randint(0, 2, (n,), device=dev).float()
+
+
+def store_cost(torch, dev, repeats, n=1 << 20, T=16, capacities=(10000, 1 << 20)):
+    from merging_gym import PrioritizedRainbowReplay, RainbowReplay
+
+    obs_first = torch.rand((n, 10), device=dev)
+    obs, rew = torch.rand((T, n, 10), device=dev), torch.rand((T, n, 2), device=dev)
+    a1 = torch.randint(0, 5, (T, n), device=dev).to(torch.int8)
+    done = (torch.rand((T, n), device=dev) < 0.01).to(torch.uint8)
+    out = {"n": n, "num_steps": T, "capacities": {}}
+    for cap in capacities:
+        rings = {"uniform_us": RainbowReplay(cap, device=dev), "prioritized_us": PrioritizedRainbowReplay(cap, 0.6, device=dev)}
+        runs = {k: [] for k in rings}
+        for rep_ in range(repeats + 1):  # the first pass warms up
+            for k, ring in rings.items():
+                t = timed(torch, lambda: ring.store(obs_first, obs, a1, rew, done, obs))
+                if rep_:
+                    runs[k].append(t)
+        out["capacities"][str(cap)] = {**{k: min(v) for k, v in runs.items()}, **{k + "_runs": v for k, v in runs.items()}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rainbow_learn_bench.json"))
@@ -160,7 +193,7 @@ def main():
 
     import torch
 
-    from merging_gym import RainbowLearner, RainbowReplay, _native
+    from merging_gym import PrioritizedRainbowLearner, PrioritizedRainbowReplay, RainbowLearner, RainbowReplay, _native
 
     if not torch.cuda.is_available():
         sys.exit("rainbow_learn_bench needs the GPU: a time taken elsewhere says nothing")
@@ -170,24 +203,36 @@ def main():
     for batch in BATCHES:
         torch.manual_seed(0)
         replay = RainbowReplay(10000, device=dev)
-        replay.memory.copy_(torch.rand(replay.memory.shape, device=dev) * 10.0)
-        replay.memory[:, 10] = torch.randint(0, 5, (10000,), device=dev).float()
-        replay.memory[:, 22] = torch.randint(0, 2, (10000,), device=dev).float()
+        fill(torch, replay, dev)
         replay._counter.fill_(10000)
+        per = PrioritizedRainbowReplay(10000, 0.6, device=dev)
+        per.store(torch.rand((10000, 10), device=dev), torch.rand((1, 10000, 10), device=dev),
+                  torch.zeros((1, 10000), dtype=torch.int8, device=dev), torch.rand((1, 10000, 2), device=dev))
+        per.memory.copy_(replay.memory)
+        for r in range(64):
+            idx, _ = per.sample_indices(1024, 0.4, seed=2, draw=r)
+            per.update_priorities(idx, torch.rand(1024, device=dev) * 4.0 + 1e-3)
         net, torch_learn = torch_rainbow(torch, dev)
         learner = RainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, replay, batch_size=batch)
+        plearner = PrioritizedRainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, per, batch_size=batch)
         learner.learn(args.warmup)
+        plearner.learn(args.warmup)
         for _ in range(args.warmup):
             torch_learn(replay, batch)
-        ours, ref = [], []
+        ours, ref, prio = [], [], []
         for _ in range(args.repeats):  # alternating, so drift of the shared machine hits both
             ours.append(timed(torch, lambda: learner.learn(args.updates)) / args.updates)
+            prio.append(timed(torch, lambda: plearner.learn(args.updates)) / args.updates)
             ref.append(timed(torch, lambda: [torch_learn(replay, batch) for _ in range(args.updates)]) / args.updates)
         entry = {"batch": batch, "ours_us": min(ours), "ours_us_runs": ours, "torch_us": min(ref), "torch_us_runs": ref,
                  "launches": LAUNCHES, "per_launch_us": min(ours) / LAUNCHES,
-                 "speedup_vs_torch": min(ref) / min(ours), "kernels": kernel_breakdown(torch, learner)}
+                 "speedup_vs_torch": min(ref) / min(ours), "kernels": kernel_breakdown(torch, learner),
+                 "prioritized_us": min(prio), "prioritized_us_runs": prio, "prioritized_launches": PER_LAUNCHES,
+                 "prioritized_kernels": kernel_breakdown(torch, plearner)}
         result["batches"][f"b{batch}"] = entry
         print(json.dumps({f"b{batch}": entry}), flush=True)
+    result["store"] = store_cost(torch, dev, args.repeats)
+    print(json.dumps({"store": result["store"]}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
