@@ -49,6 +49,11 @@
  *   mg_host_rainbow_learn / mg_host_rainbow_project / mg_host_rainbow_log: ranbowdqn.py's ReplayBuffer.push
  *                     (:281-288) and compute_td_loss (:554-609) -- C51 projection, noisy-net backward, Adam,
  *                     the noise reset; fp32 in a documented order
+ *   mg_per_* / mg_rainbow_learn_prioritized: PrioritizedReplayBuffer (:326-437) and its segment trees
+ *                     (:130-262) beside those rows, and compute_td_loss drawing from them
+ *   mg_rainbow_noise / mg_host_rainbow_noise / mg_rainbow_ndtri / mg_host_rainbow_ndtri: the factors of
+ *                     RainbowDQN.reset_noise (:486-496, :537-541) drawn on the device from a counter-based
+ *                     stream in a documented order, and its inverse normal CDF alone
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -847,6 +852,42 @@ int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const u
                                       float* loss_out, float* rows_out, float* proj_out, float* grads_out,
                                       void* scratch, size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha,
                                       double beta, double prio_eps, int64_t* idx_out, float* weight_out);
+
+/* ---- Rainbow noise on the device (additive to ABI 21) -----------------------------------------------
+ * The factors mg_rainbow_learn and mg_rainbow_learn_prioritized read from `noise`, drawn by a kernel instead of
+ * 24 host torch.randn calls per update: mg_rainbow_noise fills noise_out [num_updates][2][1124] fp32 (the layout
+ * above: model 0 current, 1 target; per noisy layer eps_in [64], eps_out [out], the bias noise [out], in
+ * reset_noise's layer order) on the stream. The stream of numbers is counter-based: element (u, m, f) is a pure
+ * function of (noise_seed, t = first_update + u, m, f), there is no generator state and no rejection loop, and any
+ * element can be drawn on its own. The distribution is torch.randn's (a standard normal through _scale_noise);
+ * the numbers are not torch's. In this fixed order, every operation rounded once, no contraction, no fma:
+ *   1. words    w0, w1 = words x, y of Philox4x32-10 with key noise_seed and counter (b, t), as mg_replay_sample's
+ *               block (low word first), with b = 2^63 | (m * 1124 + f). The minibatch draws use b < 1024, so the
+ *               two streams never share a counter, also where noise_seed equals the learner's seed.
+ *   2. uniform  k = ((uint64)(w0 >> 6) << 26) | (w1 >> 6), 52 bits; u = (k + 0.5) * 2^-52, exact in fp64. u is
+ *               never 0, 0.5 or 1, and 1 - u is exact too.
+ *   3. normal   z = Phi^-1(u) in fp64 by Wichura's algorithm AS 241, routine PPND16, with the coefficients as
+ *               CPython's statistics.py (_normal_dist_inv_cdf) writes them. q = u - 0.5.
+ *               |q| <= 0.425: r = 0.180625 - q * q; z = (A(r) * q) / B(r).
+ *               otherwise: p = u where q < 0, else 1 - u; r = sqrt(-log(p)) with the fp64 log of the prioritized
+ *               replay's pow above (fdlibm's e_log.c) and a correctly rounded sqrt;
+ *               r <= 5: r' = r - 1.6, z = C(r') / D(r'); r > 5: r' = r - 5, z = E(r') / F(r'); z negated where
+ *               q < 0.
+ *               Each polynomial c0 + c1 r + ... + c7 r^7 is evaluated in Horner form from c7 down,
+ *               acc = acc * r + c_i (a rounded product, then a rounded sum); the numerator first, then the
+ *               denominator, then one division. No library transcendental.
+ *   4. factor   x = fp32(z), rounded to nearest; the factor is sqrtf(x) for x > 0 and -sqrtf(-x) for x < 0 --
+ *               _scale_noise's x.sign().mul(x.abs().sqrt()) (:493-496), elementwise. x is never 0.
+ * mg_rainbow_ndtri: z[i] = that Phi^-1 of u[i] on DEVICE pointers (a probe: the r > 5 branch needs u < e^-25,
+ * which no small stream reaches). NaN for u outside (0, 1), for a NaN and for a subnormal u (the log takes normal
+ * numbers). ndtri(1 - u) == -ndtri(u) bit for bit wherever 1 - u is exact, as for every u of step 2.
+ * mg_host_rainbow_noise / mg_host_rainbow_ndtri: the same functions on HOST pointers, synchronously.
+ * Refused: a NULL pointer, num_updates < 0 or n < 0, noise_out not 4-byte or u / z not 8-byte aligned. A count of 0
+ * is accepted and does nothing. */
+int mg_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* noise_out, void* stream);
+int mg_host_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* noise_out);
+int mg_rainbow_ndtri(const double* u, double* z, int64_t n, void* stream);
+int mg_host_rainbow_ndtri(const double* u, double* z, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@
 #include "mg_learn.h"           // DQN.learn: the minibatch update kernels, their launch order and host twin
 #include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
 #include "mg_per.h"             // prioritized replay: the sum / min trees, store, sample, update, the weighted learner
+#include "mg_rainbow_noise.h"   // the learner's noise factors drawn on the device: Philox, inverse normal CDF, host twin
 
 extern "C" {
 
@@ -870,6 +871,35 @@ int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const u
     per_learn_set_update(Q, L, u);
     host_per_learn_update(Q, L);
   }
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- Rainbow noise on the device (the factors of RainbowDQN.reset_noise, :486-496, :537-541) --------
+int mg_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* noise_out, void* stream) {
+  if (int e = check_rainbow_noise("mg_rainbow_noise", num_updates, noise_out)) return e;
+  if (num_updates == 0) return 0;
+  launch_rainbow_noise(noise_seed, first_update, num_updates, noise_out, static_cast<hipStream_t>(stream));
+  return finish_launch("mg_rainbow_noise");
+}
+
+int mg_host_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* noise_out) {
+  if (int e = check_rainbow_noise("mg_host_rainbow_noise", num_updates, noise_out)) return e;
+  host_rainbow_noise(noise_seed, first_update, num_updates, noise_out);
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_rainbow_ndtri(const double* u, double* z, int64_t n, void* stream) {
+  if (int e = check_rainbow_ndtri("mg_rainbow_ndtri", u, z, n)) return e;
+  if (n == 0) return 0;
+  launch_rainbow_ndtri(u, z, n, static_cast<hipStream_t>(stream));
+  return finish_launch("mg_rainbow_ndtri");
+}
+
+int mg_host_rainbow_ndtri(const double* u, double* z, int64_t n) {
+  if (int e = check_rainbow_ndtri("mg_host_rainbow_ndtri", u, z, n)) return e;
+  host_rainbow_ndtri(u, z, n);
   g_err[0] = '\0';
   return 0;
 }

@@ -24,7 +24,8 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .rainbow import RainbowNet
 
         return RainbowNet
-    if name in ("RainbowReplay", "RainbowLearner", "PrioritizedRainbowReplay", "PrioritizedRainbowLearner"):
+    if name in ("RainbowReplay", "RainbowLearner", "PrioritizedRainbowReplay", "PrioritizedRainbowLearner",
+                "DeviceNoise"):
         from . import rainbow_learn
 
         return getattr(rainbow_learn, name)

@@ -225,6 +225,13 @@ def _load(path=LIB_PATH):
               lib.mg_host_per_sample, lib.mg_per_update, lib.mg_host_per_update, lib.mg_host_per_total,
               lib.mg_host_per_pow, lib.mg_rainbow_learn_prioritized, lib.mg_host_rainbow_learn_prioritized):
         f.restype = _c.c_int
+    # Rainbow noise on the device (additive to ABI 21): the factors' stream, its inverse normal CDF, host twins
+    lib.mg_rainbow_noise.argtypes = [_c.c_uint64, _c.c_uint64, _c.c_int32, _P, _P]
+    lib.mg_host_rainbow_noise.argtypes = [_c.c_uint64, _c.c_uint64, _c.c_int32, _P]
+    lib.mg_rainbow_ndtri.argtypes = [_P, _P, _c.c_int64, _P]
+    lib.mg_host_rainbow_ndtri.argtypes = [_P, _P, _c.c_int64]
+    for f in (lib.mg_rainbow_noise, lib.mg_host_rainbow_noise, lib.mg_rainbow_ndtri, lib.mg_host_rainbow_ndtri):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

@@ -80,16 +80,33 @@ class RainbowNet:
                                          if self.training else mu)
         return out
 
-    def reset_noise(self, generator=None):
+    def reset_noise(self, generator=None, *, seed=None, draw=0):
         """RainbowDQN.reset_noise (:537-541): per noisy layer epsilon_in, epsilon_out, then the bias noise, each
         one torch.randn (:486-496). generator=None draws from torch's global generator, so after the same
-        torch.manual_seed and the same earlier draws the buffers equal the reference's."""
+        torch.manual_seed and the same earlier draws the buffers equal the reference's.
+
+        seed: take the factors from the counter-based stream of a DeviceNoise learner instead
+        (rainbow_learn.device_noise_factors): the current model's block of update `draw`, so the buffers equal
+        those of a learner with generator=DeviceNoise(seed) after its update number `draw` (counted from 0)."""
+        if seed is not None and generator is not None:
+            raise ValueError("reset_noise takes a generator or a seed, not both")
+        if seed is not None:
+            from .rainbow_learn import device_noise_factors
+
+            factors, at = device_noise_factors(1, seed, draw)[0, 0], 0
+
+            def take(size, _generator):
+                nonlocal at
+                at += size
+                return factors[at - size:at]
+        else:
+            take = _scale_noise
         for name in NOISY:
             out_f, in_f = SHAPES[name]
-            eps_in = _scale_noise(in_f, generator)
-            eps_out = _scale_noise(out_f, generator)
+            eps_in = take(in_f, generator)
+            eps_out = take(out_f, generator)
             self.state[f"{name}.weight_epsilon"].copy_(eps_out.ger(eps_in))
-            self.state[f"{name}.bias_epsilon"].copy_(_scale_noise(out_f, generator))
+            self.state[f"{name}.bias_epsilon"].copy_(take(out_f, generator))
         self._packed = None
 
     # ---- device side

@@ -18,7 +18,14 @@ the loop of ranbowdqn.py:662-691 closes without leaving the device:
 
 The arithmetic is fp32 in the fixed order include/merging_hip.h documents, so a run is reproducible bit for
 bit, also across a state_dict() / load_state_dict() resume. The noise is torch's: every update consumes the
-draws of two RainbowNet.reset_noise calls (the current model's, then the target's) from `generator`.
+draws of two RainbowNet.reset_noise calls (the current model's, then the target's) from `generator`. With
+generator=DeviceNoise(noise_seed) a kernel draws the factors instead, from a counter-based stream keyed by
+(noise_seed, update index) that include/merging_hip.h documents at mg_rainbow_noise: learn() then does no host
+work and no upload, and the distribution, not the numbers, is torch's:
+
+    learner = RainbowLearner(sd, replay, generator=DeviceNoise(7))
+    learner.learn(4)                                       # enqueued behind the rollout and the store
+    actor = RainbowNet.from_state_dict(sd); actor.reset_noise(seed=7, draw=3)   # the current model's noise now
 
 PrioritizedRainbowReplay and PrioritizedRainbowLearner are the same pair over the script's
 PrioritizedReplayBuffer (:326-437) and its sum / min segment trees (:130-262), which the script defines and
@@ -114,6 +121,37 @@ def noise_factors(num_updates, generator=None):
             torch.randn(size, generator=generator, out=flat[at:at + size])
             at += size
     return out.sign().mul_(out.abs().sqrt_())  # _scale_noise's x.sign().mul(x.abs().sqrt()), elementwise
+
+
+class DeviceNoise:
+    """The noise source of a learner that draws its factors on the device: pass it where a learner takes its
+    `generator`. seed: the stream's key (None: the learner's minibatch seed). The stream is counter-based and
+    has no state, so one DeviceNoise may serve several learners."""
+
+    def __init__(self, seed=None):
+        self.seed = None if seed is None else int(seed) & U64
+
+    def __repr__(self):
+        return f"DeviceNoise(seed={self.seed})"
+
+
+def device_noise_factors(num_updates, noise_seed, first_update=0):
+    """[num_updates, 2, 1124] fp32 on the CPU, in noise_factors' layout: the factors a DeviceNoise learner with
+    this noise_seed draws for its updates first_update, first_update + 1, ... (libmerging_hip.so's
+    mg_host_rainbow_noise, the host twin of the kernel: the same bits). The stream is counter-based -- element
+    (u, model, factor) depends on (noise_seed, first_update + u, model, factor) alone -- so there is no state."""
+    import torch
+
+    from . import _native
+
+    U = int(num_updates)
+    if U < 0:
+        raise ValueError("num_updates must be >= 0")
+    out = torch.empty((U, 2, NUM_FACTORS), dtype=torch.float32)
+    if U > 0:  # an empty tensor has no storage to point at
+        rc = _native.lib.mg_host_rainbow_noise(int(noise_seed) & U64, int(first_update) & U64, U, out.data_ptr())
+        _native.check(rc, "mg_host_rainbow_noise")
+    return out
 
 
 class RainbowReplay(RingBase):
@@ -294,7 +332,7 @@ class _LearnerNet(RainbowNet):
     def packed(self):
         return self._learner._packed
 
-    def reset_noise(self, generator=None):
+    def reset_noise(self, generator=None, *, seed=None, draw=0):
         raise RuntimeError("the learner owns this net's noise: RainbowLearner.learn() redraws it")
 
 
@@ -307,14 +345,19 @@ class RainbowLearner(LearnerBase):
         """net: a RainbowNet, or a RainbowDQN.state_dict(); the current and the target model both start from
         it, noise included (update_target, :648). replay: the RainbowReplay learn() draws from. lr, gamma,
         batch_size: ranbowdqn.py:645, :569, :652. seed: the key of the minibatch draws (update u draws what
-        replay.sample(batch_size, seed, draw=u) returns). generator: the torch.Generator of the noise draws
-        (None: torch's global one, as the reference). A PrioritizedRainbowReplay takes the subclass
+        replay.sample(batch_size, seed, draw=u) returns). generator: the source of the noise draws -- a
+        torch.Generator (None: torch's global one, as the reference), drawn from on the host, or a
+        DeviceNoise(noise_seed), drawn by a kernel on the stream. A PrioritizedRainbowReplay takes the subclass
         PrioritizedRainbowLearner."""
         super().__init__(replay, "replay memory", device)
         torch, _native = self._torch, self._nat
         self.replay = replay
         sd = net.state if isinstance(net, RainbowNet) else net
-        self.generator = generator
+        if isinstance(generator, DeviceNoise):  # self.noise: "torch" or "device", the mode a state dict names
+            self.noise, self.generator = "device", None
+            self.noise_seed = (int(seed) if generator.seed is None else generator.seed) & U64
+        else:
+            self.noise, self.noise_seed, self.generator = "torch", None, generator
         assert int(_native.lib.mg_rainbow_learner_bytes()) == 4 * LEARNER_FLOATS
         self._buf = learner_array(sd).to(self.device)
         if isinstance(replay, PrioritizedRainbowReplay) != self._prioritized:
@@ -360,13 +403,24 @@ class RainbowLearner(LearnerBase):
         loss, rows = new(return_loss, U), new(return_rows, U, B, ROW)
         proj, grads = new(return_proj, U, B, NUM_ATOMS), new(return_grads, U, NUM_PARAMS)
         if U > 0:
-            noise = noise_factors(U, self.generator).to(self.device)
+            noise = self._noise(U)
             self._call(U, noise, loss, rows, proj, grads, extra)
             self._keepalive = noise
             self.learn_step_counter += U
             self.draw_counter += U
         out = tuple(t for t in (loss, rows, proj, grads, *more) if t is not None)
         return None if not out else out[0] if len(out) == 1 else out
+
+    def _noise(self, U):
+        """The [U, 2, 1124] factors of the next U updates on the device: torch's draws uploaded, or in device
+        mode mg_rainbow_noise's on the current stream (nothing drawn or copied on the host)."""
+        if self.noise == "torch":
+            return noise_factors(U, self.generator).to(self.device)
+        out = self._torch.empty((U, 2, NUM_FACTORS), dtype=self._torch.float32, device=self.device)
+        rc = self._nat.lib.mg_rainbow_noise(self.noise_seed, self.learn_step_counter & U64, U, out.data_ptr(),
+                                            self._stream())
+        self._nat.check(rc, "mg_rainbow_noise")
+        return out
 
     def sync_target(self):
         """update_target (:551-552, :690-691): target := current, noise included."""
@@ -383,12 +437,22 @@ class RainbowLearner(LearnerBase):
 
     def state_dict(self):
         """Both models with their noise, Adam's moments, the counters and the noise generator's state: a run
-        resumed from it continues bit for bit."""
+        resumed from it continues bit for bit. In device mode the noise needs no state beyond the counters: the
+        dict carries "noise": "device" and "noise_seed" in the generator's place."""
+        if self.noise == "device":
+            return dict(super().state_dict(), noise="device", noise_seed=self.noise_seed)
         return dict(super().state_dict(),
                     generator=None if self.generator is None else self.generator.get_state())
 
     def load_state_dict(self, sd):
+        theirs = sd.get("noise", "torch")
+        if theirs != self.noise:
+            raise ValueError(f'the state is of a learner with "{theirs}" noise, this learner draws "{self.noise}" '
+                             'noise ("torch": a torch.Generator on the host, "device": a DeviceNoise): build the '
+                             "learner in the state's mode")
         super().load_state_dict(sd)
+        if self.noise == "device":
+            self.noise_seed = int(sd["noise_seed"]) & U64
         if sd.get("generator") is not None:
             if self.generator is None:
                 self.generator = self._torch.Generator()
@@ -412,8 +476,9 @@ class PrioritizedRainbowLearner(RainbowLearner):
     def __init__(self, net, replay, lr: float = 0.001, gamma: float = 0.99, batch_size: int = 32, seed: int = 0,
                  generator=None, device=None, betas=(0.9, 0.999), eps: float = 1e-8, beta: float = 0.4,
                  prio_eps: float = 1e-5):
-        """RainbowLearner's arguments, then beta: the importance weights' exponent (learn() may override it per
-        call), prio_eps: added to a row's loss to give its new priority."""
+        """RainbowLearner's arguments (generator: a torch.Generator or a DeviceNoise), then beta: the importance
+        weights' exponent (learn() may override it per call), prio_eps: added to a row's loss to give its new
+        priority."""
         if not (beta > 0 and prio_eps >= 0):
             raise ValueError("beta must be > 0 and prio_eps >= 0")
         self.beta, self.prio_eps = float(beta), float(prio_eps)

@@ -6,6 +6,10 @@ Per batch size (32, the reference's, and 128) in one process on one GPU:
   ours_us        microseconds per update of RainbowLearner.learn(updates): HIP events around one call that draws
                  the noise factors on the host, uploads them once and enqueues every update, after `warmup`
                  untimed updates;
+  device_noise_us
+                 the same call of a RainbowLearner(generator=DeviceNoise()): the factors drawn by
+                 rainbow_noise_kernel on the stream (one launch per call, not per update), no host draw and no
+                 upload; timed exactly as ours_us, alternating with it;
   torch_us       ranbowdqn.py's compute_td_loss (:554-609) in eager torch on device tensors -- both forwards,
                  the projection with index_add_, the clamped cross-entropy, Adam, both reset_noise calls (drawn
                  on the host as the reference draws them) -- fed by RainbowReplay.sample, timed the same way;
@@ -15,7 +19,8 @@ Per batch size (32, the reference's, and 128) in one process on one GPU:
   launches       kernel launches per update and per_launch_us = ours_us / launches;
   kernels        per kernel, the mean device time of one launch and the launches per update, from
                  torch.profiler's kernel records of a separate pass of 20 updates. null if the profiler gave
-                 no kernel records.
+                 no kernel records. The rainbow_noise_kernel row is the device-noise learner's (the host-noise
+                 learner never launches it); device_noise_kernels is that learner's whole breakdown.
 "store": one store of n = 2^20 envs x T = 16 steps through mg_rainbow_replay_store (uniform_us) and through
 mg_per_store (prioritized_us: the rows, the written leaves, their ancestors level by level), per ring capacity.
 Best of `repeats` alternating runs. The replay memory holds seeded random rows and the nets their default
@@ -139,7 +144,7 @@ def kernel_breakdown(torch, learner, updates=20):
             torch.cuda.synchronize()
         rows = {}
         for ev in prof.events():
-            m = re.search(r"(rl_\w+_kernel|learn_\w+_kernel|per_\w+_kernel|rainbow_pack_kernel)", ev.name)
+            m = re.search(r"(rl_\w+_kernel|learn_\w+_kernel|per_\w+_kernel|rainbow_pack_kernel|rainbow_noise_kernel)", ev.name)
             if not m:
                 continue
             t = getattr(ev, "device_time", None)
@@ -193,7 +198,7 @@ def main():
 
     import torch
 
-    from merging_gym import PrioritizedRainbowLearner, PrioritizedRainbowReplay, RainbowLearner, RainbowReplay, _native
+    from merging_gym import DeviceNoise, PrioritizedRainbowLearner, PrioritizedRainbowReplay, RainbowLearner, RainbowReplay, _native
 
     if not torch.cuda.is_available():
         sys.exit("rainbow_learn_bench needs the GPU: a time taken elsewhere says nothing")
@@ -215,20 +220,30 @@ def main():
         net, torch_learn = torch_rainbow(torch, dev)
         learner = RainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, replay, batch_size=batch)
         plearner = PrioritizedRainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, per, batch_size=batch)
+        dlearner = RainbowLearner({k: v.detach() for k, v in net.state_dict().items()}, replay, batch_size=batch,
+                                  generator=DeviceNoise())
         learner.learn(args.warmup)
+        dlearner.learn(args.warmup)
         plearner.learn(args.warmup)
         for _ in range(args.warmup):
             torch_learn(replay, batch)
-        ours, ref, prio = [], [], []
+        ours, ref, prio, devn = [], [], [], []
         for _ in range(args.repeats):  # alternating, so drift of the shared machine hits both
             ours.append(timed(torch, lambda: learner.learn(args.updates)) / args.updates)
+            devn.append(timed(torch, lambda: dlearner.learn(args.updates)) / args.updates)
             prio.append(timed(torch, lambda: plearner.learn(args.updates)) / args.updates)
             ref.append(timed(torch, lambda: [torch_learn(replay, batch) for _ in range(args.updates)]) / args.updates)
         entry = {"batch": batch, "ours_us": min(ours), "ours_us_runs": ours, "torch_us": min(ref), "torch_us_runs": ref,
                  "launches": LAUNCHES, "per_launch_us": min(ours) / LAUNCHES,
                  "speedup_vs_torch": min(ref) / min(ours), "kernels": kernel_breakdown(torch, learner),
                  "prioritized_us": min(prio), "prioritized_us_runs": prio, "prioritized_launches": PER_LAUNCHES,
-                 "prioritized_kernels": kernel_breakdown(torch, plearner)}
+                 "prioritized_kernels": kernel_breakdown(torch, plearner),
+                 "device_noise_us": min(devn), "device_noise_us_runs": devn,
+                 "device_noise_vs_ours": min(devn) / min(ours),
+                 "device_noise_kernels": kernel_breakdown(torch, dlearner)}
+        noise_row = (entry["device_noise_kernels"] or {}).get("rainbow_noise_kernel")
+        if noise_row and isinstance(entry["kernels"], dict) and "error" not in entry["kernels"]:
+            entry["kernels"]["rainbow_noise_kernel"] = noise_row
         result["batches"][f"b{batch}"] = entry
         print(json.dumps({f"b{batch}": entry}), flush=True)
     result["store"] = store_cost(torch, dev, args.repeats)
