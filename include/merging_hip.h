@@ -40,6 +40,9 @@
  *   mg_host_dqn_learn (ABI 21): DQN.learn (scripts/main.py:122-157; HDQN.learn hdqn.py:186-221,
  *                     Goal_DQN.learn hdqn.py:104-139) -- the minibatch update from the replay ring:
  *                     Double-DQN target, MSE, Adam, the target copy; fp32 in a documented order
+ *   mg_dqn_learn_many / mg_dqn_learn_many_init / mg_dqn_learn_many_table_bytes / mg_host_dqn_learn_many: up to
+ *                     64 such learners of one shape, each on its own net, memory, seed and hyperparameters,
+ *                     in the same seven launches; every member bit for bit a lone mg_dqn_learn
  *   mg_rainbow_pack / mg_rainbow_packed_bytes / mg_rainbow_forward / mg_host_rainbow_head: RainbowDQN's
  *                     acting forward (scripts/ranbowdqn.py:517-548: noisy dueling C51 net, act()) -- bf16
  *                     MFMA layers, the distributional head in fp32 in a documented order
@@ -616,6 +619,60 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
                       uint64_t first_update, uint64_t seed, uint64_t first_draw, int32_t filled_only,
                       const mg_dqn_hyper* hyper, float* loss_out, float* rows_out, void* scratch,
                       size_t scratch_bytes);
+
+/* ---- A population of DQN learners in one set of launches (additive to ABI 21) -----------------------
+ * `members` (1 .. 64) independent learners of one shape (in_dim, out_dim, batch, capacity), each on its
+ * own net, memory, seed, counters and hyperparameters, trained by the same launches: one update of all
+ * members is mg_dqn_learn's seven launches with the member in the grid, an eighth (the target copy, under
+ * a 64-bit member mask) when any member's copy is due, and the repack of all eval nets is two launches
+ * per call. Nothing in mg_dqn_learn_many synchronises or copies from the host.
+ *
+ * Contract: for every member m, the effect on its learner block, its losses, its rows and its packed net
+ * is bit for bit that of mg_dqn_learn on that member's buffers with that member's seed, first_update,
+ * first_draw and hyper (the kernels rebase the member and run the same per-element functions). K updates
+ * in one call equal K calls.
+ *
+ * Member state is contiguous: learners [members, 4 P] fp32 (member m's block is an mg_dqn_learn learner),
+ * scratch [members, mg_dqn_learn_scratch_bytes(batch, in_dim, out_dim)], packed_out [members,
+ * packed_stride] bytes (optional; packed_stride a multiple of 16, >= mg_qnet_packed_bytes()). Each member's
+ * ring and counter come by pointer in its mg_dqn_member, so members may share one ring (it is only read).
+ * loss_out [num_updates, members] and rows_out [num_updates, members, batch, row_floats] are optional.
+ *
+ * `member` is a HOST array of `members` entries. What does not change from update to update -- rows,
+ * counter, seed, gamma, Adam's betas and eps, each rounded as mg_dqn_learn rounds it -- lives in a device
+ * table of mg_dqn_learn_many_table_bytes(members) bytes (16-byte aligned) that mg_dqn_learn_many_init
+ * writes on `stream` from the same array; call it again after changing any of those fields. Each
+ * update's draw index, Adam's step and bias-correction scalars (from the host's doubles, libm pow) and
+ * the copy mask travel in the kernel argument. On success mg_dqn_learn_many and mg_host_dqn_learn_many
+ * advance every member's first_update and first_draw by num_updates, so the next call continues the run.
+ * mg_host_dqn_learn_many is the loop over members of mg_host_dqn_learn's update, on HOST pointers, and
+ * needs no table.
+ *
+ * Refused before anything is read or launched: members outside 1 .. 64, NULL pointers (counter only with
+ * filled_only), what mg_dqn_learn refuses of the shape, any member's target_period < 1 or betas outside
+ * [0, 1) (the text names the member), misaligned pointers or stride (learners, scratch, table, packed_out
+ * 16-byte; every member's rows and counter 8-byte; loss_out, rows_out 4-byte), scratch smaller than
+ * members * mg_dqn_learn_scratch_bytes, table smaller than mg_dqn_learn_many_table_bytes. */
+typedef struct mg_dqn_member {
+  const float* rows;       /* the member's ring [capacity, row_floats] */
+  const uint64_t* counter; /* its counter (read only with filled_only) */
+  uint64_t seed;           /* key of its minibatch draws */
+  uint64_t first_update;   /* updates it has made: Adam's step count - 1, the target copy's clock */
+  uint64_t first_draw;     /* minibatches it has drawn */
+  mg_dqn_hyper hyper;
+} mg_dqn_member;
+
+size_t mg_dqn_learn_many_table_bytes(int32_t members); /* 0 outside 1 .. 64 */
+int mg_dqn_learn_many_init(void* table, size_t table_bytes, const mg_dqn_member* member, int32_t members,
+                           void* stream);
+int mg_dqn_learn_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member, int32_t members,
+                      int64_t capacity, int32_t row_floats, int32_t in_dim, int32_t out_dim, int32_t batch,
+                      int32_t num_updates, int32_t filled_only, float* loss_out, float* rows_out, void* packed_out,
+                      size_t packed_stride, void* scratch, size_t scratch_bytes, void* stream);
+int mg_host_dqn_learn_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                           int32_t row_floats, int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates,
+                           int32_t filled_only, float* loss_out, float* rows_out, void* scratch,
+                           size_t scratch_bytes);
 
 /* ---- Rainbow acting (additive to ABI 21) ------------------------------------------------------------
  * The acting path of scripts/ranbowdqn.py: RainbowDQN.forward / act (:517-548) and the loop that calls

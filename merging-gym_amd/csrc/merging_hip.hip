@@ -47,6 +47,7 @@
 #include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
 #include "mg_per.h"             // prioritized replay: the sum / min trees, store, sample, update, the weighted learner
 #include "mg_rainbow_noise.h"   // the learner's noise factors drawn on the device: Philox, inverse normal CDF, host twin
+#include "mg_learn_many.h"      // a population of DQN learners: mg_learn.h's launches with the member in the grid
 
 extern "C" {
 
@@ -517,6 +518,77 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
     const uint64_t t = first_update + static_cast<uint64_t>(u);
     learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), u, loss_out, rows_out);
     host_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0);
+  }
+  g_err[0] = '\0';
+  return 0;
+}
+
+// ---- a population of DQN learners in mg_dqn_learn's launches ---------------------------------------
+size_t mg_dqn_learn_many_table_bytes(int32_t members) {
+  return members_ok(members) ? sizeof(LearnMember) * static_cast<size_t>(members) : 0;
+}
+
+int mg_dqn_learn_many_init(void* table, size_t table_bytes, const mg_dqn_member* member, int32_t members,
+                           void* stream) {
+  if (int e = check_members("mg_dqn_learn_many_init", member, members, 0)) return e;
+  if (int e = check_member_table("mg_dqn_learn_many_init", table, table_bytes, members)) return e;
+  for (int m = 0; m < members; ++m)  // by value, on the stream: nothing is copied from the caller's memory later
+    hipLaunchKernelGGL(learn_many_entry_kernel, dim3(1), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       static_cast<LearnMember*>(table) + m, learn_member_entry(member[m]));
+  return finish_launch("mg_dqn_learn_many_init");
+}
+
+int mg_dqn_learn_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member, int32_t members,
+                      int64_t capacity, int32_t row_floats, int32_t in_dim, int32_t out_dim, int32_t batch,
+                      int32_t num_updates, int32_t filled_only, float* loss_out, float* rows_out, void* packed_out,
+                      size_t packed_stride, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int e = check_learn_many("mg_dqn_learn_many", learners, member, members, capacity, row_floats, in_dim, out_dim,
+                               batch, num_updates, filled_only, loss_out, rows_out, packed_out, packed_stride, scratch,
+                               scratch_bytes))
+    return e;
+  if (int e = check_member_table("mg_dqn_learn_many", table, table_bytes, members)) return e;
+  if (num_updates == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LearnMany Q = make_learn_many(learners, static_cast<const LearnMember*>(table), members, capacity, in_dim, out_dim,
+                                batch, filled_only, scratch);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    learn_many_set_update(Q, member, u, loss_out, rows_out);
+    launch_learn_many_update(Q, st);
+  }
+  if (packed_out) {  // the acting kernels' layouts of all the new eval nets, on the same stream
+    const unsigned M = static_cast<unsigned>(members);
+    const int total = kQFrags * 64 * 8, total32 = kQ32R1 * kQ32S1 + kQ32R2 * kQ32S2 + kQ32R3 * kQ32S3;
+    hipLaunchKernelGGL(qnet_pack_many_kernel, dim3((total + 255) / 256, M), dim3(256), 0, st, learners, in_dim,
+                       out_dim, static_cast<uint8_t*>(packed_out), static_cast<int64_t>(packed_stride));
+    hipLaunchKernelGGL(qnet32_pack_many_kernel, dim3((total32 + 255) / 256, M), dim3(256), 0, st, learners, in_dim,
+                       out_dim, static_cast<uint8_t*>(packed_out), static_cast<int64_t>(packed_stride));
+  }
+  if (int e = finish_launch("mg_dqn_learn_many")) return e;
+  for (int m = 0; m < members; ++m) {
+    member[m].first_update += static_cast<uint64_t>(num_updates);
+    member[m].first_draw += static_cast<uint64_t>(num_updates);
+  }
+  return 0;
+}
+
+int mg_host_dqn_learn_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                           int32_t row_floats, int32_t in_dim, int32_t out_dim, int32_t batch, int32_t num_updates,
+                           int32_t filled_only, float* loss_out, float* rows_out, void* scratch,
+                           size_t scratch_bytes) {
+  if (int e = check_learn_many("mg_host_dqn_learn_many", learners, member, members, capacity, row_floats, in_dim,
+                               out_dim, batch, num_updates, filled_only, loss_out, rows_out, nullptr, 0, scratch,
+                               scratch_bytes))
+    return e;
+  LearnMember table[kLMaxMembers];
+  for (int m = 0; m < members; ++m) table[m] = learn_member_entry(member[m]);
+  LearnMany Q = make_learn_many(learners, table, members, capacity, in_dim, out_dim, batch, filled_only, scratch);
+  for (int32_t u = 0; u < num_updates; ++u) {
+    learn_many_set_update(Q, member, u, loss_out, rows_out);
+    host_learn_many_update(Q);
+  }
+  for (int m = 0; m < members; ++m) {
+    member[m].first_update += static_cast<uint64_t>(num_updates);
+    member[m].first_draw += static_cast<uint64_t>(num_updates);
   }
   g_err[0] = '\0';
   return 0;

@@ -158,11 +158,10 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 }
 
 // Packs fp32 torch Linear weights (row-major [out][in]) and biases into the fragment layout above:
-// one thread per (fragment, lane, element).
-__global__ void qnet_pack_kernel(const float* w1, const float* b1, const float* w2, const float* b2,
-                                 const float* w3, const float* b3, int in_dim, int out_dim,
-                                 uint8_t* packed) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+// element e of (fragment, lane, element).
+__device__ __forceinline__ void qnet_pack_at(int e, const float* w1, const float* b1, const float* w2, const float* b2,
+                                             const float* w3, const float* b3, int in_dim, int out_dim,
+                                             uint8_t* packed) {
   if (e >= kQFrags * 64 * 8) return;
   const int s = e >> 9, lane = (e >> 3) & 63, j = e & 7;
   const QFrag f = qfrag(s);
@@ -193,6 +192,13 @@ __global__ void qnet_pack_kernel(const float* w1, const float* b1, const float* 
     off = qfrag_off(s) + 16 * (8 * (lane >> 4) + m);
   }
   reinterpret_cast<__bf16*>(packed + off)[j] = static_cast<__bf16>(v);
+}
+
+// One thread per (fragment, lane, element).
+__global__ void qnet_pack_kernel(const float* w1, const float* b1, const float* w2, const float* b2,
+                                 const float* w3, const float* b3, int in_dim, int out_dim,
+                                 uint8_t* packed) {
+  qnet_pack_at(blockIdx.x * blockDim.x + threadIdx.x, w1, b1, w2, b2, w3, b3, in_dim, out_dim, packed);
 }
 
 // A zero the compiler cannot see through. Added to the LDS addresses of loop-invariant
@@ -514,11 +520,10 @@ __device__ __forceinline__ bf16x8 relu_bf16(const f32x16& c, int s) {
                                           relu_pair(c[b + 4], c[b + 5]), relu_pair(c[b + 6], c[b + 7])});
 }
 
-// Packs fp32 torch Linear weights (row-major [out][in]) and biases into the kernel layout.
-__global__ void qnet32_pack_kernel(const float* w1, const float* b1, const float* w2, const float* b2,
-                                 const float* w3, const float* b3, int in_dim, int out_dim,
-                                 uint8_t* packed) {
-  int e = blockIdx.x * blockDim.x + threadIdx.x;
+// Packs fp32 torch Linear weights (row-major [out][in]) and biases into the kernel layout: element e.
+__device__ __forceinline__ void qnet32_pack_at(int e, const float* w1, const float* b1, const float* w2,
+                                               const float* b2, const float* w3, const float* b3, int in_dim,
+                                               int out_dim, uint8_t* packed) {
   __bf16* pw1 = reinterpret_cast<__bf16*>(packed);
   __bf16* pw2 = reinterpret_cast<__bf16*>(packed + kQ32OffW2);
   __bf16* pw3 = reinterpret_cast<__bf16*>(packed + kQ32OffW3);
@@ -562,6 +567,12 @@ __global__ void qnet32_pack_kernel(const float* w1, const float* b1, const float
     }
     pw3[e] = static_cast<__bf16>(v);
   }
+}
+
+__global__ void qnet32_pack_kernel(const float* w1, const float* b1, const float* w2, const float* b2,
+                                 const float* w3, const float* b3, int in_dim, int out_dim,
+                                 uint8_t* packed) {
+  qnet32_pack_at(blockIdx.x * blockDim.x + threadIdx.x, w1, b1, w2, b2, w3, b3, in_dim, out_dim, packed);
 }
 
 // Rows 0-3 of the env of lane 32t + r sit in registers 0-3 of lane half 0 of column tile t,

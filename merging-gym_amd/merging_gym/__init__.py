@@ -20,6 +20,10 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .learn import DQNLearner
 
         return DQNLearner
+    if name == "DQNPopulation":
+        from .population import DQNPopulation
+
+        return DQNPopulation
     if name == "RainbowNet":
         from .rainbow import RainbowNet
 

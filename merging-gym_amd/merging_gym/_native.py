@@ -73,6 +73,13 @@ class DqnHyper(_c.Structure):
                 ("eps", _c.c_double), ("target_period", _c.c_int32), ("reserved", _c.c_int32)]
 
 
+class DqnMember(_c.Structure):
+    """struct mg_dqn_member: one learner of a population (mg_dqn_learn_many) -- its ring and counter by
+    pointer, its seed, its counters (the calls advance them) and its mg_dqn_hyper."""
+    _fields_ = [("rows", _P), ("counter", _P), ("seed", _c.c_uint64), ("first_update", _c.c_uint64),
+                ("first_draw", _c.c_uint64), ("hyper", DqnHyper)]
+
+
 class Stats(_c.Structure):
     _fields_ = [("rec", _P)]  # mg_episode_stats [n] (64 bytes each, see EPISODE_STATS_DTYPE)
 
@@ -172,6 +179,16 @@ def _load(path=LIB_PATH):
     lib.mg_dqn_learn.argtypes = learn_args + [_P, _P, _c.c_size_t, _P]
     lib.mg_host_dqn_learn.argtypes = learn_args + [_P, _c.c_size_t]
     for f in (lib.mg_dqn_learner_init, lib.mg_dqn_learn, lib.mg_host_dqn_learn):
+        f.restype = _c.c_int
+    # a population of DQN learners in the same launches (additive to ABI 21)
+    MP = _c.POINTER(DqnMember)
+    lib.mg_dqn_learn_many_table_bytes.argtypes = [_c.c_int32]
+    lib.mg_dqn_learn_many_table_bytes.restype = _c.c_size_t
+    lib.mg_dqn_learn_many_init.argtypes = [_P, _c.c_size_t, MP, _c.c_int32, _P]
+    many_args = [MP, _c.c_int32, _c.c_int64] + [_c.c_int32] * 6 + [_P, _P]
+    lib.mg_dqn_learn_many.argtypes = [_P, _P, _c.c_size_t] + many_args + [_P, _c.c_size_t, _P, _c.c_size_t, _P]
+    lib.mg_host_dqn_learn_many.argtypes = [_P] + many_args + [_P, _c.c_size_t]
+    for f in (lib.mg_dqn_learn_many_init, lib.mg_dqn_learn_many, lib.mg_host_dqn_learn_many):
         f.restype = _c.c_int
     # Rainbow acting (additive to ABI 21): the packed net, its forward, the fused rollout, the host head
     lib.mg_rainbow_packed_bytes.restype = _c.c_size_t

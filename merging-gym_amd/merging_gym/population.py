@@ -1,0 +1,254 @@
+"""DQNPopulation: M independent DQNLearners trained by one set of launches.
+
+What the reference's users do with its scripts is train many agents -- sweeps over the reward parameters,
+L1 against L0 and then against L1, hdqn.py's two nets -- and one DQNLearner.learn() is a dependent chain
+of seven small launches that leaves most of the device idle. A population runs M learners of one shape
+through the same seven launches (libmerging_hip.so's mg_dqn_learn_many), each on its own net, replay
+ring, seed, counters and hyperparameters:
+
+    rings = [ReplayRing(2000, device="cuda:0") for _ in range(8)]
+    pop = DQNPopulation([sd] * 8, rings, lr=[0.01, 0.005, 0.02, 0.01, 0.01, 0.01, 0.01, 0.01], seed=range(8))
+    traj = envs[m].rollout_qnet(16, pop.qnets[m], seed)     # member m acts with its own net
+    rings[m].store_rollout(obs0, traj)
+    pop.learn(4)                                            # four updates of all eight members
+    pop.copy_member(best, worst)                            # population-based training's exploit step
+
+Member m is bit for bit the lone DQNLearner built from the same net, ring, seed and hyperparameters:
+member_state_dict(m) is that learner's state_dict() and loads into one, and back.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+from . import _native
+from ._device import U64, cuda_device, ptr, raw_stream, require_gpu
+from .learn import KEYS
+from .policy import QNet
+
+MAX_MEMBERS = 64
+
+
+def _per_member(value, members, name, pair=False):
+    """`value` for every member: a scalar (a pair, for betas) applied to all, or a sequence of `members`."""
+    shared = not hasattr(value, "__len__") and not hasattr(value, "__iter__")
+    if pair:
+        value = list(value)
+        shared = len(value) == 2 and not hasattr(value[0], "__len__")
+    if shared:
+        return [value] * members
+    value = list(value)
+    if len(value) != members:
+        raise ValueError(f"{name}: expected one value or {members}, got {len(value)}")
+    return value
+
+
+class DQNPopulation:
+    def __init__(self, nets, rings, lr=0.01, gamma=0.9, batch_size: int = 128, target_period=100,
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, device=None):
+        """nets: M QNets or state dicts with the reference's keys (fc1.weight ... out.bias), all of one
+        shape. rings: M ReplayRings of one capacity and row width on one device; the same ring may appear
+        more than once (learn() only reads it). lr, gamma, target_period, betas, eps and seed are each one
+        value applied to every member -- the seed too, so members on one ring with one seed draw the same
+        minibatches -- or a sequence of M. batch_size is shared."""
+        torch = require_gpu(type(self).__name__)
+        self._torch = torch
+        nets, rings = list(nets), list(rings)
+        M = len(nets)
+        if not 1 <= M <= MAX_MEMBERS:
+            raise ValueError(f"a population has 1..{MAX_MEMBERS} members, got {M}")
+        if len(rings) != M:
+            raise ValueError(f"{M} nets need {M} rings (one ring may appear more than once), got {len(rings)}")
+        self.device = cuda_device(torch, device, rings[0].device)
+        ring0 = rings[0]
+        for r in rings:
+            if r.device != self.device:
+                raise ValueError(f"a ring lives on {r.device}, the population on {self.device}")
+            if (r.capacity, r.row) != (ring0.capacity, ring0.row):
+                raise ValueError("the rings of a population share one capacity and row width")
+        self.rings = rings
+        tensors = []
+        for net in nets:
+            if isinstance(net, QNet):
+                if torch.device(net.device.type, net.device.index or 0) != self.device:
+                    raise ValueError(f"a QNet lives on {net.device}, the population on {self.device}")
+                tensors.append(list(net.fp32))
+            else:
+                tensors.append([torch.as_tensor(net[k], dtype=torch.float32).to(self.device).contiguous()
+                                for k in KEYS])
+        self.in_dim, self.out_dim = int(tensors[0][0].shape[1]), int(tensors[0][4].shape[0])
+        for ts in tensors:
+            if (int(ts[0].shape[1]), int(ts[4].shape[0])) != (self.in_dim, self.out_dim):
+                raise ValueError("the nets of a population share one shape")
+        if ring0.row != 2 * self.in_dim + 2:
+            raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
+                             f"the rings' have {ring0.row}")
+        lib = _native.lib
+        nbytes = int(lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
+        if nbytes == 0:
+            raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
+        self.batch_size = int(batch_size)
+        one = int(lib.mg_dqn_learn_scratch_bytes(self.batch_size, self.in_dim, self.out_dim))
+        if one == 0:
+            raise ValueError("batch_size must be in 1..1024")
+        self._P = nbytes // 16
+        lrs, gammas, epss = (_per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
+        periods, seeds = _per_member(target_period, M, "target_period"), _per_member(seed, M, "seed")
+        pairs = _per_member(betas, M, "betas", pair=True)
+        self._members = (_native.DqnMember * M)()
+        for m in range(M):
+            self._members[m] = _native.DqnMember(
+                rings[m].memory.data_ptr(), rings[m]._counter.data_ptr(), int(seeds[m]) & U64, 0, 0,
+                _native.DqnHyper(float(lrs[m]), float(gammas[m]), float(pairs[m][0]), float(pairs[m][1]),
+                                 float(epss[m]), int(periods[m]), 0))
+        self._buf = torch.empty((M, 4 * self._P), dtype=torch.float32, device=self.device)
+        self._scratch_bytes = one * M
+        self._scratch = torch.empty(self._scratch_bytes // 4, dtype=torch.float32, device=self.device)
+        self._stride = int(lib.mg_qnet_packed_bytes())
+        self._packed = torch.empty((M, self._stride), dtype=torch.uint8, device=self.device)
+        self._table_bytes = int(lib.mg_dqn_learn_many_table_bytes(M))
+        self._table = torch.empty(self._table_bytes, dtype=torch.uint8, device=self.device)
+        self._write_table()
+        # the acting nets: their fp32 tensors are views of the members' eval blocks, their packed
+        # buffers rows of one buffer that every learn() rewrites
+        self.qnets = []
+        for m, (net, ts) in enumerate(zip(nets, tensors)):
+            _native.check(lib.mg_dqn_learner_init(self._buf[m].data_ptr(), *(t.data_ptr() for t in ts), self.in_dim,
+                                                  self.out_dim, self._stream()), "mg_dqn_learner_init")
+            qnet = net if isinstance(net, QNet) else QNet(*self._views(m, 0), device=self.device)
+            qnet.fp32 = self._views(m, 0)
+            qnet.packed = self._packed[m]
+            self.qnets.append(qnet)
+            self._repack(m)
+
+    # ------------------------------------------------------------------ helpers
+    def __len__(self):
+        return len(self._members)
+
+    def _stream(self):
+        return raw_stream(self._torch, self.device)
+
+    def _write_table(self):
+        """The device's member table (rings, seeds, gamma, Adam's constants) from the member list."""
+        _native.check(_native.lib.mg_dqn_learn_many_init(self._table.data_ptr(), self._table_bytes, self._members,
+                                                         len(self._members), self._stream()),
+                      "mg_dqn_learn_many_init")
+
+    def _views(self, m, block):
+        """The six tensors of member m's block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
+        flat = self._buf[m, block * self._P:(block + 1) * self._P]
+        shapes = ((200, self.in_dim), (200,), (100, 200), (100,), (self.out_dim, 100), (self.out_dim,))
+        out, at = [], 0
+        for s in shapes:
+            n = s[0] * (s[1] if len(s) == 2 else 1)
+            out.append(flat[at:at + n].view(s))
+            at += n
+        return out
+
+    def _repack(self, m):
+        _native.check(_native.lib.mg_qnet_pack(*(t.data_ptr() for t in self._views(m, 0)), self.in_dim, self.out_dim,
+                                               self._packed[m].data_ptr(), self._stream()), "mg_qnet_pack")
+        self.qnets[m].__dict__.pop("_reset_argmax", None)
+
+    @property
+    def learn_step_counter(self):
+        """Per member, the updates made so far (Adam's step count, the target copy's clock)."""
+        return [int(e.first_update) for e in self._members]
+
+    @property
+    def draw_counter(self):
+        """Per member, the minibatches drawn so far."""
+        return [int(e.first_draw) for e in self._members]
+
+    @property
+    def seed(self):
+        return [int(e.seed) for e in self._members]
+
+    # ------------------------------------------------------------------ learn
+    def learn(self, num_updates: int = 1, filled_only: bool = False, return_loss: bool = False,
+              return_rows: bool = False):
+        """num_updates updates of every member, enqueued back to back on the current stream: seven launches
+        per update of the whole population (eight when a member's target copy is due), two per call for
+        the acting nets; nothing is synchronised. filled_only draws from the rows each member's ring has
+        stored so far. return_loss: the [num_updates, M] fp32 device tensor of the MSE losses; return_rows:
+        also the [num_updates, M, B, row] minibatches."""
+        torch = self._torch
+        U, M = int(num_updates), len(self._members)
+        if U < 0:
+            raise ValueError("num_updates must be >= 0")
+        row = self.rings[0].row
+        loss = torch.empty((U, M), dtype=torch.float32, device=self.device) if return_loss else None
+        rows = torch.empty((U, M, self.batch_size, row), dtype=torch.float32,
+                           device=self.device) if return_rows else None
+        if U > 0:
+            rc = _native.lib.mg_dqn_learn_many(
+                self._buf.data_ptr(), self._table.data_ptr(), self._table_bytes, self._members, M,
+                self.rings[0].capacity, row, self.in_dim, self.out_dim, self.batch_size, U, 1 if filled_only else 0,
+                ptr(loss), ptr(rows), self._packed.data_ptr(), self._stride, self._scratch.data_ptr(),
+                self._scratch_bytes, self._stream())
+            _native.check(rc, "mg_dqn_learn_many")  # the call advanced the members' counters
+            for q in self.qnets:
+                q.__dict__.pop("_reset_argmax", None)
+        if return_loss and return_rows:
+            return loss, rows
+        return loss if return_loss else rows
+
+    # ------------------------------------------------------------------ checkpoints
+    def eval_state_dict(self, m):
+        """Member m's eval_net.state_dict() as main.py:244 saves it (copies, torch-loadable)."""
+        return {k: t.clone() for k, t in zip(KEYS, self._views(m, 0))}
+
+    def target_state_dict(self, m):
+        """Member m's target_net.state_dict() as main.py:245 saves it."""
+        return {k: t.clone() for k, t in zip(KEYS, self._views(m, 1))}
+
+    def member_state_dict(self, m):
+        """Exactly the state_dict() of the lone DQNLearner member m equals: it loads into one."""
+        e = self._members[m]
+        return {"learner": self._buf[m].clone(), "learn_step_counter": int(e.first_update),
+                "draw_counter": int(e.first_draw), "seed": int(e.seed), "in_dim": self.in_dim,
+                "out_dim": self.out_dim}
+
+    def load_member_state_dict(self, m, sd):
+        """A DQNLearner's state_dict() (or member_state_dict()) into member m: nets, moments, counters, seed."""
+        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim):
+            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
+        buf = self._torch.as_tensor(sd["learner"])
+        if buf.numel() != 4 * self._P:
+            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
+        self._buf[m].copy_(buf.to(self._torch.float32).reshape(-1))
+        e = self._members[m]
+        e.first_update, e.first_draw = int(sd["learn_step_counter"]), int(sd["draw_counter"])
+        e.seed = int(sd["seed"]) & U64
+        self._write_table()
+        self._repack(m)
+
+    def state_dict(self):
+        """Every member's nets, moments, counters and seed: a run resumed from it continues bit for bit."""
+        return {"learners": self._buf.clone(), "learn_step_counter": self.learn_step_counter,
+                "draw_counter": self.draw_counter, "seed": self.seed, "in_dim": self.in_dim,
+                "out_dim": self.out_dim}
+
+    def load_state_dict(self, sd):
+        buf = self._torch.as_tensor(sd["learners"])
+        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim) or \
+                tuple(buf.shape) != tuple(self._buf.shape):
+            raise ValueError(f"expected the state of {len(self)} {self.in_dim} -> {self.out_dim} learners")
+        self._buf.copy_(buf.to(self._torch.float32))
+        for m, e in enumerate(self._members):
+            e.first_update, e.first_draw = int(sd["learn_step_counter"][m]), int(sd["draw_counter"][m])
+            e.seed = int(sd["seed"][m]) & U64
+        self._write_table()
+        for m in range(len(self)):
+            self._repack(m)
+
+    def copy_member(self, src, dst):
+        """Population-based training's exploit step: dst takes src's nets, Adam moments and counters (a
+        device-side copy) and is repacked for acting; it keeps its own seed, ring and hyperparameters."""
+        src, dst = int(src), int(dst)
+        if src == dst:
+            return
+        self._buf[dst].copy_(self._buf[src])
+        self._members[dst].first_update = self._members[src].first_update
+        self._members[dst].first_draw = self._members[src].first_draw
+        self._repack(dst)
