@@ -43,11 +43,11 @@
 #include "mg_stats_reduce.h"    // the fixed-order statistics reduction, goal_status_kernel
 #include "mg_host_env.h"        // the CPU single-env path
 #include "mg_learn_core.h"      // the fixed-order fp32 primitives both learners share, learn_bwd_kernel
-#include "mg_learn.h"           // DQN.learn: the minibatch update kernels, their launch order and host twin
+#include "mg_learn.h"           // DQN.learn, lone and population: the update kernels with the member in the grid,
+                                // their launch order, host twin and the drivers of a call
 #include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
 #include "mg_per.h"             // prioritized replay: the sum / min trees, store, sample, update, the weighted learner
 #include "mg_rainbow_noise.h"   // the learner's noise factors drawn on the device: Philox, inverse normal CDF, host twin
-#include "mg_learn_many.h"      // a population of DQN learners: mg_learn.h's launches with the member in the grid
 
 extern "C" {
 
@@ -164,13 +164,11 @@ int mg_qnet_pack(const float* fc1_w, const float* fc1_b, const float* fc2_w, con
   if (int e = check_net_dims("mg_qnet_pack", in_dim, out_dim)) return e;
   if (misaligned(packed, 15))
     return fail(hipErrorInvalidValue, "%s", "mg_qnet_pack: packed buffer must be 16-byte aligned");
-  const int total = kQFrags * 64 * 8;  // one thread per (fragment, lane, element)
-  hipLaunchKernelGGL(qnet_pack_kernel, dim3((total + 255) / 256), dim3(256), 0,
+  hipLaunchKernelGGL(qnet_pack_kernel, dim3(kQPackBlocks), dim3(kQPackBlock), 0,
                      static_cast<hipStream_t>(stream), fc1_w, fc1_b, fc2_w, fc2_b, out_w, out_b,
                      in_dim, out_dim, static_cast<uint8_t*>(packed));
   // the 32x32 layout behind it (qnet32_mlp: the config-5 kernel without a net opponent)
-  const int total32 = kQ32R1 * kQ32S1 + kQ32R2 * kQ32S2 + kQ32R3 * kQ32S3;
-  hipLaunchKernelGGL(qnet32_pack_kernel, dim3((total32 + 255) / 256), dim3(256), 0,
+  hipLaunchKernelGGL(qnet32_pack_kernel, dim3(kQ32PackBlocks), dim3(kQPackBlock), 0,
                      static_cast<hipStream_t>(stream), fc1_w, fc1_b, fc2_w, fc2_b, out_w, out_b,
                      in_dim, out_dim, static_cast<uint8_t*>(packed) + kQNetBytes);
   return finish_launch("mg_qnet_pack");
@@ -490,19 +488,10 @@ int mg_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int
   if (int e = check_learn("mg_dqn_learn", learner, rows, counter, capacity, row_floats, in_dim, out_dim, batch,
                           num_updates, filled_only, hyper, loss_out, rows_out, packed_out, scratch, scratch_bytes))
     return e;
-  if (num_updates == 0) return 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
-  const LearnLayout O = learn_layout(in_dim, out_dim);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    const uint64_t t = first_update + static_cast<uint64_t>(u);
-    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), u, loss_out, rows_out);
-    launch_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0, st);
-  }
-  if (packed_out)  // the acting kernels' layout of the new eval net, on the same stream
-    return mg_qnet_pack(L.eval + O.w1, L.eval + O.b1, L.eval + O.w2, L.eval + O.b2, L.eval + O.w3, L.eval + O.b3,
-                        in_dim, out_dim, packed_out, stream);
-  return finish_launch("mg_dqn_learn");
+  mg_dqn_member one{rows, counter, seed, first_update, first_draw, *hyper};  // the population of one, no table
+  LearnMany Q = make_learn_many(learner, nullptr, &one, 1, capacity, in_dim, out_dim, batch, filled_only, scratch);
+  return learn_many_device("mg_dqn_learn", Q, &one, num_updates, loss_out, rows_out, packed_out,
+                           mg_qnet_packed_bytes(), static_cast<hipStream_t>(stream));
 }
 
 int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t row_floats,
@@ -512,15 +501,9 @@ int mg_host_dqn_learn(float* learner, const float* rows, const uint64_t* counter
   if (int e = check_learn("mg_host_dqn_learn", learner, rows, counter, capacity, row_floats, in_dim, out_dim, batch,
                           num_updates, filled_only, hyper, loss_out, rows_out, nullptr, scratch, scratch_bytes))
     return e;
-  Learn L = make_learn(learner, rows, counter, capacity, in_dim, out_dim, batch, seed, filled_only, hyper, scratch);
-  const LearnLayout O = learn_layout(in_dim, out_dim);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    const uint64_t t = first_update + static_cast<uint64_t>(u);
-    learn_set_update(L, hyper, t, first_draw + static_cast<uint64_t>(u), u, loss_out, rows_out);
-    host_learn_update(L, O, t % static_cast<uint64_t>(hyper->target_period) == 0);
-  }
-  g_err[0] = '\0';
-  return 0;
+  mg_dqn_member one{rows, counter, seed, first_update, first_draw, *hyper};
+  LearnMany Q = make_learn_many(learner, nullptr, &one, 1, capacity, in_dim, out_dim, batch, filled_only, scratch);
+  return learn_many_host(Q, &one, num_updates, loss_out, rows_out);
 }
 
 // ---- a population of DQN learners in mg_dqn_learn's launches ---------------------------------------
@@ -547,28 +530,10 @@ int mg_dqn_learn_many(float* learners, const void* table, size_t table_bytes, mg
                                scratch_bytes))
     return e;
   if (int e = check_member_table("mg_dqn_learn_many", table, table_bytes, members)) return e;
-  if (num_updates == 0) return 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  LearnMany Q = make_learn_many(learners, static_cast<const LearnMember*>(table), members, capacity, in_dim, out_dim,
-                                batch, filled_only, scratch);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    learn_many_set_update(Q, member, u, loss_out, rows_out);
-    launch_learn_many_update(Q, st);
-  }
-  if (packed_out) {  // the acting kernels' layouts of all the new eval nets, on the same stream
-    const unsigned M = static_cast<unsigned>(members);
-    const int total = kQFrags * 64 * 8, total32 = kQ32R1 * kQ32S1 + kQ32R2 * kQ32S2 + kQ32R3 * kQ32S3;
-    hipLaunchKernelGGL(qnet_pack_many_kernel, dim3((total + 255) / 256, M), dim3(256), 0, st, learners, in_dim,
-                       out_dim, static_cast<uint8_t*>(packed_out), static_cast<int64_t>(packed_stride));
-    hipLaunchKernelGGL(qnet32_pack_many_kernel, dim3((total32 + 255) / 256, M), dim3(256), 0, st, learners, in_dim,
-                       out_dim, static_cast<uint8_t*>(packed_out), static_cast<int64_t>(packed_stride));
-  }
-  if (int e = finish_launch("mg_dqn_learn_many")) return e;
-  for (int m = 0; m < members; ++m) {
-    member[m].first_update += static_cast<uint64_t>(num_updates);
-    member[m].first_draw += static_cast<uint64_t>(num_updates);
-  }
-  return 0;
+  LearnMany Q = make_learn_many(learners, static_cast<const LearnMember*>(table), member, members, capacity, in_dim,
+                                out_dim, batch, filled_only, scratch);
+  return learn_many_device("mg_dqn_learn_many", Q, member, num_updates, loss_out, rows_out, packed_out, packed_stride,
+                           static_cast<hipStream_t>(stream));
 }
 
 int mg_host_dqn_learn_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
@@ -581,17 +546,9 @@ int mg_host_dqn_learn_many(float* learners, mg_dqn_member* member, int32_t membe
     return e;
   LearnMember table[kLMaxMembers];
   for (int m = 0; m < members; ++m) table[m] = learn_member_entry(member[m]);
-  LearnMany Q = make_learn_many(learners, table, members, capacity, in_dim, out_dim, batch, filled_only, scratch);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    learn_many_set_update(Q, member, u, loss_out, rows_out);
-    host_learn_many_update(Q);
-  }
-  for (int m = 0; m < members; ++m) {
-    member[m].first_update += static_cast<uint64_t>(num_updates);
-    member[m].first_draw += static_cast<uint64_t>(num_updates);
-  }
-  g_err[0] = '\0';
-  return 0;
+  LearnMany Q =
+      make_learn_many(learners, table, member, members, capacity, in_dim, out_dim, batch, filled_only, scratch);
+  return learn_many_host(Q, member, num_updates, loss_out, rows_out);
 }
 
 // ---- Rainbow acting (scripts/ranbowdqn.py:517-548, :662-680) ----------------------------------------

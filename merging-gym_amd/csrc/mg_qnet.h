@@ -575,6 +575,12 @@ __global__ void qnet32_pack_kernel(const float* w1, const float* b1, const float
   qnet32_pack_at(blockIdx.x * blockDim.x + threadIdx.x, w1, b1, w2, b2, w3, b3, in_dim, out_dim, packed);
 }
 
+// The grids of the two pack launches (mg_qnet_pack, the DQN learners' repack): one thread per packed element.
+constexpr int kQPackBlock = 256;
+constexpr unsigned kQPackBlocks = (kQFrags * 64 * 8 + kQPackBlock - 1) / kQPackBlock;  // (fragment, lane, element)
+constexpr unsigned kQ32PackBlocks =
+    (kQ32R1 * kQ32S1 + kQ32R2 * kQ32S2 + kQ32R3 * kQ32S3 + kQPackBlock - 1) / kQPackBlock;
+
 // Rows 0-3 of the env of lane 32t + r sit in registers 0-3 of lane half 0 of column tile t,
 // rows 4-7 in lane half 1. One v_permlane32_swap per register pair (gfx950) exchanges tile 0's
 // upper half with tile 1's lower half: afterwards register j of the first operand holds row j and

@@ -1,7 +1,9 @@
 """What the two replay rings (ReplayRing, RainbowReplay) and the two learners (DQNLearner, RainbowLearner)
-share: the device buffers, the stream, the sample call, the counters and the checkpoint code."""
+share: the device buffers, the stream, the sample call, the counters and the checkpoint code; and what
+DQNLearner and DQNPopulation share of a DQN net's handling (DQNNets)."""
 
 from ._device import U64, cuda_device, raw_stream, require_gpu
+from .policy import QNet
 
 
 class RingBase:
@@ -107,3 +109,73 @@ class LearnerBase:
         self.learn_step_counter = int(sd["learn_step_counter"])
         self.draw_counter = int(sd["draw_counter"])
         self.seed = int(sd["seed"]) & U64
+
+
+DQN_KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "out.weight", "out.bias")
+
+
+class DQNNets:
+    """What DQNLearner and DQNPopulation share: a net's intake, the shape checks, the views of a flat [4 P]
+    learner buffer, its repack for acting and the check of a learner's state. Uses _torch, _nat, device, _stream()."""
+
+    def _net_tensors(self, net, a, owner):
+        """A QNet or a state dict with the reference's keys as six contiguous fp32 tensors on the device."""
+        torch = self._torch
+        if isinstance(net, QNet):
+            if torch.device(net.device.type, net.device.index or 0) != self.device:
+                raise ValueError(f"{a} QNet lives on {net.device}, the {owner} on {self.device}")
+            return list(net.fp32)
+        return [torch.as_tensor(net[k], dtype=torch.float32).to(self.device).contiguous() for k in DQN_KEYS]
+
+    def _set_shape(self, tensors, row, rings):
+        """in_dim, out_dim and _P (the floats of one block) of a net, which must fit the rows it learns from."""
+        self.in_dim, self.out_dim = int(tensors[0].shape[1]), int(tensors[4].shape[0])
+        if row != 2 * self.in_dim + 2:
+            raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
+                             f"the {rings} have {row}")
+        nbytes = int(self._nat.lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
+        if nbytes == 0:
+            raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
+        self._P = nbytes // 16
+
+    def _block_views(self, learner, block):
+        """The six tensors of a learner's block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
+        shapes = ((200, self.in_dim), (200,), (100, 200), (100,), (self.out_dim, 100), (self.out_dim,))
+        parts = learner[block * self._P:(block + 1) * self._P].split([s[0] * (s[1:] or (1,))[0] for s in shapes])
+        return [p.view(s) for p, s in zip(parts, shapes)]
+
+    def _init_learner(self, learner, net, tensors, packed=None):
+        """Fills a learner buffer from a net's tensors (eval = target, zero moments) and returns its acting net:
+        `net` itself if it is a QNet, its fp32 tensors now views of the eval block; with `packed`, packing there."""
+        rc = self._nat.lib.mg_dqn_learner_init(learner.data_ptr(), *(t.data_ptr() for t in tensors), self.in_dim,
+                                               self.out_dim, self._stream())
+        self._nat.check(rc, "mg_dqn_learner_init")
+        qnet = net if isinstance(net, QNet) else QNet(*self._block_views(learner, 0), device=self.device)
+        qnet.fp32 = self._block_views(learner, 0)
+        if packed is not None:
+            qnet.packed = packed
+            self._pack(learner, qnet)
+        self._new_weights(qnet)
+        return qnet
+
+    def _net_state_dict(self, learner, block):
+        return {k: t.clone() for k, t in zip(DQN_KEYS, self._block_views(learner, block))}
+
+    @staticmethod
+    def _new_weights(qnet):
+        """The acting net's weights changed: what it derived from the old ones goes."""
+        qnet.__dict__.pop("_reset_argmax", None)
+
+    def _pack(self, learner, qnet):
+        """The learner's eval block into qnet's packed buffer, for the acting kernels."""
+        rc = self._nat.lib.mg_qnet_pack(*(t.data_ptr() for t in self._block_views(learner, 0)), self.in_dim,
+                                        self.out_dim, qnet.packed.data_ptr(), self._stream())
+        self._nat.check(rc, "mg_qnet_pack")
+        self._new_weights(qnet)
+
+    def _learner_state(self, sd):
+        """The learner buffer in a DQNLearner's state dict, as a tensor; another shape's is refused."""
+        buf = self._torch.as_tensor(sd["learner"])
+        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim) or buf.numel() != 4 * self._P:
+            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
+        return buf

@@ -24,14 +24,11 @@ from __future__ import annotations
 import ctypes
 
 from . import _native
-from ._base import LearnerBase
+from ._base import DQNNets, LearnerBase
 from ._device import ptr
-from .policy import QNet
-
-KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "out.weight", "out.bias")
 
 
-class DQNLearner(LearnerBase):
+class DQNLearner(DQNNets, LearnerBase):
     def __init__(self, net, ring, lr: float = 0.01, gamma: float = 0.9, batch_size: int = 128,
                  target_period: int = 100, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, device=None):
         """net: a QNet, or a state dict with the reference's keys (fc1.weight ... out.bias); both
@@ -42,51 +39,18 @@ class DQNLearner(LearnerBase):
         super().__init__(ring, "ring", device)
         torch = self._torch
         self.ring = ring
-        if isinstance(net, QNet):
-            if net.device != self.device and torch.device(net.device.type, net.device.index or 0) != self.device:
-                raise ValueError(f"the QNet lives on {net.device}, the learner on {self.device}")
-            tensors, qnet = list(net.fp32), net
-        else:
-            tensors = [torch.as_tensor(net[k], dtype=torch.float32).to(self.device).contiguous() for k in KEYS]
-            qnet = None
-        self.in_dim, self.out_dim = int(tensors[0].shape[1]), int(tensors[4].shape[0])
-        if ring.row != 2 * self.in_dim + 2:
-            raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
-                             f"the ring's have {ring.row}")
-        self._state_of = f"a {self.in_dim} -> {self.out_dim} learner"
-        nbytes = int(_native.lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
-        if nbytes == 0:
-            raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
+        tensors = self._net_tensors(net, "the", "learner")
+        self._set_shape(tensors, ring.row, "ring's")
         self.target_period = int(target_period)
         sbytes = int(_native.lib.mg_dqn_learn_scratch_bytes(int(batch_size), self.in_dim, self.out_dim))
         self._setup(batch_size, seed, sbytes, lr, gamma, betas, eps, self.target_period)
-        self._P = nbytes // 16
         self._buf = torch.empty(4 * self._P, dtype=torch.float32, device=self.device)
-        _native.check(_native.lib.mg_dqn_learner_init(self._buf.data_ptr(), *(t.data_ptr() for t in tensors),
-                                                      self.in_dim, self.out_dim, self._stream()),
-                      "mg_dqn_learner_init")
         # the acting net: its fp32 tensors are views of the eval block, its packed buffer is
         # rewritten by every learn()
-        self.qnet = qnet if qnet is not None else QNet(*self._views(0), device=self.device)
-        self.qnet.fp32 = self._views(0)
-        self.qnet.__dict__.pop("_reset_argmax", None)
-
-    # ------------------------------------------------------------------ helpers
-    def _views(self, block):
-        """The six tensors of block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
-        flat = self._buf[block * self._P:(block + 1) * self._P]
-        shapes = ((200, self.in_dim), (200,), (100, 200), (100,), (self.out_dim, 100), (self.out_dim,))
-        out, at = [], 0
-        for s in shapes:
-            n = s[0] * (s[1] if len(s) == 2 else 1)
-            out.append(flat[at:at + n].view(s))
-            at += n
-        return out
+        self.qnet = self._init_learner(self._buf, net, tensors)
 
     def _repack(self):
-        _native.check(_native.lib.mg_qnet_pack(*(t.data_ptr() for t in self._views(0)), self.in_dim, self.out_dim,
-                                               self.qnet.packed.data_ptr(), self._stream()), "mg_qnet_pack")
-        self.qnet.__dict__.pop("_reset_argmax", None)
+        self._pack(self._buf, self.qnet)
 
     # ------------------------------------------------------------------ learn
     def learn(self, num_updates: int = 1, filled_only: bool = False, return_loss: bool = False, return_rows: bool = False):
@@ -112,7 +76,7 @@ class DQNLearner(LearnerBase):
             _native.check(rc, "mg_dqn_learn")
             self.learn_step_counter += U
             self.draw_counter += U
-            self.qnet.__dict__.pop("_reset_argmax", None)
+            self._new_weights(self.qnet)
         if return_loss and return_rows:
             return loss, rows
         return loss if return_loss else rows
@@ -120,18 +84,17 @@ class DQNLearner(LearnerBase):
     # ------------------------------------------------------------------ checkpoints
     def eval_state_dict(self):
         """eval_net.state_dict() as main.py:244 saves it (copies, torch-loadable)."""
-        return {k: t.clone() for k, t in zip(KEYS, self._views(0))}
+        return self._net_state_dict(self._buf, 0)
 
     def target_state_dict(self):
         """target_net.state_dict() as main.py:245 saves it."""
-        return {k: t.clone() for k, t in zip(KEYS, self._views(1))}
+        return self._net_state_dict(self._buf, 1)
 
     def state_dict(self):
         """Both nets, Adam's moments and the counters: a run resumed from it continues bit for bit."""
         return dict(super().state_dict(), in_dim=self.in_dim, out_dim=self.out_dim)
 
     def load_state_dict(self, sd):
-        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim):
-            raise ValueError(f"expected the state of {self._state_of}")
+        self._learner_state(sd)  # another shape's is refused
         super().load_state_dict(sd)
         self._repack()

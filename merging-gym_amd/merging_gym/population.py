@@ -19,12 +19,9 @@ member_state_dict(m) is that learner's state_dict() and loads into one, and back
 
 from __future__ import annotations
 
-import ctypes
-
 from . import _native
+from ._base import DQNNets
 from ._device import U64, cuda_device, ptr, raw_stream, require_gpu
-from .learn import KEYS
-from .policy import QNet
 
 MAX_MEMBERS = 64
 
@@ -43,7 +40,7 @@ def _per_member(value, members, name, pair=False):
     return value
 
 
-class DQNPopulation:
+class DQNPopulation(DQNNets):
     def __init__(self, nets, rings, lr=0.01, gamma=0.9, batch_size: int = 128, target_period=100,
                  betas=(0.9, 0.999), eps=1e-8, seed=0, device=None):
         """nets: M QNets or state dicts with the reference's keys (fc1.weight ... out.bias), all of one
@@ -52,7 +49,7 @@ class DQNPopulation:
         value applied to every member -- the seed too, so members on one ring with one seed draw the same
         minibatches -- or a sequence of M. batch_size is shared."""
         torch = require_gpu(type(self).__name__)
-        self._torch = torch
+        self._torch, self._nat = torch, _native
         nets, rings = list(nets), list(rings)
         M = len(nets)
         if not 1 <= M <= MAX_MEMBERS:
@@ -67,31 +64,15 @@ class DQNPopulation:
             if (r.capacity, r.row) != (ring0.capacity, ring0.row):
                 raise ValueError("the rings of a population share one capacity and row width")
         self.rings = rings
-        tensors = []
-        for net in nets:
-            if isinstance(net, QNet):
-                if torch.device(net.device.type, net.device.index or 0) != self.device:
-                    raise ValueError(f"a QNet lives on {net.device}, the population on {self.device}")
-                tensors.append(list(net.fp32))
-            else:
-                tensors.append([torch.as_tensor(net[k], dtype=torch.float32).to(self.device).contiguous()
-                                for k in KEYS])
-        self.in_dim, self.out_dim = int(tensors[0][0].shape[1]), int(tensors[0][4].shape[0])
-        for ts in tensors:
-            if (int(ts[0].shape[1]), int(ts[4].shape[0])) != (self.in_dim, self.out_dim):
-                raise ValueError("the nets of a population share one shape")
-        if ring0.row != 2 * self.in_dim + 2:
-            raise ValueError(f"a net on {self.in_dim} inputs learns from rows of {2 * self.in_dim + 2} floats; "
-                             f"the rings' have {ring0.row}")
+        tensors = [self._net_tensors(net, "a", "population") for net in nets]
+        if len({(int(ts[0].shape[1]), int(ts[4].shape[0])) for ts in tensors}) != 1:
+            raise ValueError("the nets of a population share one shape")
+        self._set_shape(tensors[0], ring0.row, "rings'")
         lib = _native.lib
-        nbytes = int(lib.mg_dqn_learner_bytes(self.in_dim, self.out_dim))
-        if nbytes == 0:
-            raise ValueError("expected the reference Net with 1 <= in <= 13 and 1 <= out <= 8")
         self.batch_size = int(batch_size)
         one = int(lib.mg_dqn_learn_scratch_bytes(self.batch_size, self.in_dim, self.out_dim))
         if one == 0:
             raise ValueError("batch_size must be in 1..1024")
-        self._P = nbytes // 16
         lrs, gammas, epss = (_per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
         periods, seeds = _per_member(target_period, M, "target_period"), _per_member(seed, M, "seed")
         pairs = _per_member(betas, M, "betas", pair=True)
@@ -111,15 +92,7 @@ class DQNPopulation:
         self._write_table()
         # the acting nets: their fp32 tensors are views of the members' eval blocks, their packed
         # buffers rows of one buffer that every learn() rewrites
-        self.qnets = []
-        for m, (net, ts) in enumerate(zip(nets, tensors)):
-            _native.check(lib.mg_dqn_learner_init(self._buf[m].data_ptr(), *(t.data_ptr() for t in ts), self.in_dim,
-                                                  self.out_dim, self._stream()), "mg_dqn_learner_init")
-            qnet = net if isinstance(net, QNet) else QNet(*self._views(m, 0), device=self.device)
-            qnet.fp32 = self._views(m, 0)
-            qnet.packed = self._packed[m]
-            self.qnets.append(qnet)
-            self._repack(m)
+        self.qnets = [self._init_learner(self._buf[m], nets[m], tensors[m], self._packed[m]) for m in range(M)]
 
     # ------------------------------------------------------------------ helpers
     def __len__(self):
@@ -134,21 +107,8 @@ class DQNPopulation:
                                                          len(self._members), self._stream()),
                       "mg_dqn_learn_many_init")
 
-    def _views(self, m, block):
-        """The six tensors of member m's block 0 (eval), 1 (target), 2 (Adam's m) or 3 (v): views, no copies."""
-        flat = self._buf[m, block * self._P:(block + 1) * self._P]
-        shapes = ((200, self.in_dim), (200,), (100, 200), (100,), (self.out_dim, 100), (self.out_dim,))
-        out, at = [], 0
-        for s in shapes:
-            n = s[0] * (s[1] if len(s) == 2 else 1)
-            out.append(flat[at:at + n].view(s))
-            at += n
-        return out
-
     def _repack(self, m):
-        _native.check(_native.lib.mg_qnet_pack(*(t.data_ptr() for t in self._views(m, 0)), self.in_dim, self.out_dim,
-                                               self._packed[m].data_ptr(), self._stream()), "mg_qnet_pack")
-        self.qnets[m].__dict__.pop("_reset_argmax", None)
+        self._pack(self._buf[m], self.qnets[m])  # into qnets[m].packed, row m of _packed
 
     @property
     def learn_step_counter(self):
@@ -188,7 +148,7 @@ class DQNPopulation:
                 self._scratch_bytes, self._stream())
             _native.check(rc, "mg_dqn_learn_many")  # the call advanced the members' counters
             for q in self.qnets:
-                q.__dict__.pop("_reset_argmax", None)
+                self._new_weights(q)
         if return_loss and return_rows:
             return loss, rows
         return loss if return_loss else rows
@@ -196,11 +156,11 @@ class DQNPopulation:
     # ------------------------------------------------------------------ checkpoints
     def eval_state_dict(self, m):
         """Member m's eval_net.state_dict() as main.py:244 saves it (copies, torch-loadable)."""
-        return {k: t.clone() for k, t in zip(KEYS, self._views(m, 0))}
+        return self._net_state_dict(self._buf[m], 0)
 
     def target_state_dict(self, m):
         """Member m's target_net.state_dict() as main.py:245 saves it."""
-        return {k: t.clone() for k, t in zip(KEYS, self._views(m, 1))}
+        return self._net_state_dict(self._buf[m], 1)
 
     def member_state_dict(self, m):
         """Exactly the state_dict() of the lone DQNLearner member m equals: it loads into one."""
@@ -211,12 +171,7 @@ class DQNPopulation:
 
     def load_member_state_dict(self, m, sd):
         """A DQNLearner's state_dict() (or member_state_dict()) into member m: nets, moments, counters, seed."""
-        if (int(sd["in_dim"]), int(sd["out_dim"])) != (self.in_dim, self.out_dim):
-            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
-        buf = self._torch.as_tensor(sd["learner"])
-        if buf.numel() != 4 * self._P:
-            raise ValueError(f"expected the state of a {self.in_dim} -> {self.out_dim} learner")
-        self._buf[m].copy_(buf.to(self._torch.float32).reshape(-1))
+        self._buf[m].copy_(self._learner_state(sd).to(self._torch.float32).reshape(-1))
         e = self._members[m]
         e.first_update, e.first_draw = int(sd["learn_step_counter"]), int(sd["draw_counter"])
         e.seed = int(sd["seed"]) & U64

@@ -18,8 +18,10 @@ from native_build import cc  # noqa: F401  (re-exported)
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "dqn_learn_ref.c")
 KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "out.weight", "out.bias")
-# (in_dim, out_dim, batch) of the bit-exact cases; (memory, net) each shape runs on
-CASES = [(10, 5, 128), (10, 5, 32), (10, 5, 96), (11, 5, 128), (10, 3, 128)]
+# (in_dim, out_dim, batch) of the bit-exact cases; (memory, net) each shape runs on. The last three fall off
+# the kernels' tile edges: one row; fewer rows than a layer-2 row tile or a layer-3 block (8 each) with out = 3;
+# one row past a tile, on the goal rows.
+CASES = [(10, 5, 128), (10, 5, 32), (10, 5, 96), (11, 5, 128), (10, 3, 128), (10, 5, 1), (10, 3, 5), (11, 5, 9)]
 HYPER = dict(lr=0.01, gamma=0.9, beta1=0.9, beta2=0.999, eps=1e-8)  # main.py:13-14, Adam's defaults
 
 _u64, _i64, _i32, _dbl = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
