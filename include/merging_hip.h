@@ -43,6 +43,10 @@
  *   mg_dqn_learn_many / mg_dqn_learn_many_init / mg_dqn_learn_many_table_bytes / mg_host_dqn_learn_many: up to
  *                     64 such learners of one shape, each on its own net, memory, seed and hyperparameters,
  *                     in the same seven launches; every member bit for bit a lone mg_dqn_learn
+ *   mg_rollout_qnet_many / mg_replay_store_many / mg_replay_scratch_many_bytes: the acting half of such a
+ *                     population -- up to 64 members' epsilon-greedy rollouts on slices of one env batch in
+ *                     one launch, and their transitions into 64 rings in three; every member bit for bit a
+ *                     lone mg_rollout_qnet / mg_replay_store
  *   mg_rainbow_pack / mg_rainbow_packed_bytes / mg_rainbow_forward / mg_host_rainbow_head: RainbowDQN's
  *                     acting forward (scripts/ranbowdqn.py:517-548: noisy dueling C51 net, act()) -- bf16
  *                     MFMA layers, the distributional head in fp32 in a documented order
@@ -402,6 +406,33 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
                     uint64_t greedy_threshold, int32_t opponent_mode,
                     uint64_t opp_greedy_threshold, const void* opp_net, uint32_t flags, void* stream);
 
+/* ---- a population acting in one launch (additive to ABI 21) ------------------------------------
+ * mg_rollout_qnet for `members` (1 .. 64) actors on ONE env batch of n = members * n_member envs: member m
+ * owns envs [m n_member, (m + 1) n_member) and acts there with its own net, opponent net (opponent_mode 3:
+ * any packed net of the same out_dim, another member's included -- cross-play), seed and thresholds.
+ * state, traj and stats are the whole batch's ([T, n, ...] trajectory rows, ceil(n / 64) won-mask words per
+ * step); params, opponent_mode, out_dim, first_step, num_steps, flags and env_offset are shared. The Philox
+ * env index stays env_offset + i with i the index in the whole batch, so member m is bit for bit
+ * mg_rollout_qnet on its slice alone: n = n_member, env_offset + m n_member, its mg_qnet_actor's fields.
+ * The member is a grid dimension: members * ceil(n_member / 1024) blocks, each reading its member's scalars
+ * from the kernel argument, so changing a threshold or seed between calls allocates and synchronises
+ * nothing. n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole, so two
+ * members never share one). Refused before any launch: a NULL or misaligned pointer (each member's net,
+ * and its opp_net in mode 3), members outside 1 .. 64, n_member % 64 != 0, opponent_mode outside 0 .. 3;
+ * n_member == 0 or num_steps == 0 returns 0 and launches nothing. */
+typedef struct mg_qnet_actor {
+  const void* net;      /* packed Q-net (mg_qnet_pack), 16-byte aligned */
+  const void* opp_net;  /* opponent_mode 3: the member's opponent; ignored otherwise */
+  uint64_t seed;
+  uint64_t greedy_threshold;
+  uint64_t opp_greedy_threshold;
+} mg_qnet_actor;
+
+int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                         const mg_stats* stats, int64_t n_member, int32_t members, int64_t env_offset,
+                         uint64_t first_step, int32_t num_steps, const mg_qnet_actor* actors, int32_t out_dim,
+                         int32_t opponent_mode, uint32_t flags, void* stream);
+
 /* ---- h-DQN acting loop (scripts/hdqn.py:280-323) ----------------------------------------------
  * The per-step outputs of mg_rollout_hdqn besides mg_traj, [T, n] fp32 each (NULL skips one):
  * exactly the goal columns and intrinsic reward hdqn.py's lower-level store_transition takes
@@ -494,6 +525,23 @@ size_t mg_replay_scratch_bytes(int64_t n, int32_t num_steps);
 int mg_replay_store(float* rows, uint64_t* counter, int64_t capacity, int32_t row_floats,
                     const mg_transitions* tr, int64_t n, int32_t num_steps, int32_t skip_ego_won,
                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* (additive to ABI 21) mg_replay_store for `members` (1 .. 64) rings from ONE [T, N, ...] mg_transitions,
+ * N = members * n_member: member m's transitions -- columns [m n_member, (m + 1) n_member) -- go to
+ * rows[m] / counters[m] (host arrays of device pointers) in the member's own (t, i) order, i within its
+ * slice, at slot (counter_m + k) % capacity; the skip_ego_won filter and the newest-capacity rule apply per
+ * member, then counter_m += kept_m: exactly what mg_replay_store leaves when given a contiguous copy of the
+ * slice. The tensors are read in place (rows stride by N, the won mask has ceil(N / 64) words per step);
+ * the same three launches with the member as a grid dimension. n_member must be a multiple of 64 (a
+ * member's won bits begin a mask word). 22-float rows only: goal, next_goal and meta_goal are refused, as
+ * is a ring listed twice (two members' appends to one ring have no defined order). capacity and
+ * skip_ego_won are shared. scratch: mg_replay_scratch_many_bytes(n_member, num_steps, members) =
+ * members * mg_replay_scratch_bytes(n_member, num_steps) bytes (0 for members outside 1 .. 64), 8-byte
+ * aligned. n_member == 0 or num_steps == 0 returns 0. */
+size_t mg_replay_scratch_many_bytes(int64_t n_member, int32_t num_steps, int32_t members);
+int mg_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                         int32_t row_floats, const mg_transitions* tr, int64_t n_member, int32_t num_steps,
+                         int32_t skip_ego_won, void* scratch, size_t scratch_bytes, void* stream);
 
 /* out[batch, row_floats] = rows[idx[b]], idx[b] = floor(u0 * M / 2^32) with u = Philox4x32-10(key = seed,
  * counter = (b, draw)) and M = capacity (np.random.choice(MEMORY_CAPACITY, BATCH_SIZE),

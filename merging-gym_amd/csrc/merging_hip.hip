@@ -234,6 +234,62 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
   return finish_launch("mg_rollout_qnet");
 }
 
+int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                         const mg_stats* stats, int64_t n_member, int32_t members, int64_t env_offset,
+                         uint64_t first_step, int32_t num_steps, const mg_qnet_actor* actors, int32_t out_dim,
+                         int32_t opponent_mode, uint32_t flags, void* stream) {
+  const char* const who = "mg_rollout_qnet_many: %s";
+  if (members < 1 || members > kQMaxMembers) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
+  if (n_member < 0) return fail(hipErrorInvalidValue, who, "n_member < 0");
+  if (n_member % 64 != 0)
+    return fail(hipErrorInvalidValue, who,
+                "n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole, so no "
+                "two members may share one)");
+  if (n_member > (static_cast<int64_t>(0x7fffffff) * kBlock) / members)
+    return fail(hipErrorInvalidValue, who, "members * n_member exceeds the grid limit");
+  const int64_t n = n_member * members;
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (!actors) return fail(hipErrorInvalidValue, who, "actors is NULL (members mg_qnet_actor entries)");
+  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
+    return fail(hipErrorInvalidValue, who, "need num_steps >= 0 and 1 <= out_dim <= 8");
+  if (opponent_mode < 0 || opponent_mode > 3)
+    return fail(hipErrorInvalidValue, who,
+                "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (each member's opp_net)");
+  for (int m = 0; m < members; ++m) {
+    if (!actors[m].net || misaligned(actors[m].net, 15)) {
+      std::snprintf(g_err, sizeof(g_err), "mg_rollout_qnet_many: member %d: net must be a 16-byte aligned packed Q-net", m);
+      return static_cast<int>(hipErrorInvalidValue);
+    }
+    if (opponent_mode == 3 && (!actors[m].opp_net || misaligned(actors[m].opp_net, 15))) {
+      std::snprintf(g_err, sizeof(g_err),
+                    "mg_rollout_qnet_many: member %d: opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net", m);
+      return static_cast<int>(hipErrorInvalidValue);
+    }
+  }
+  if (int e = check_traj(traj)) return e;
+  if (n_member == 0 || num_steps == 0) return 0;
+  QRolloutMany A{};
+  A.R = make_rollout<QRollout>(params, state, traj, stats, 0, first_step, env_offset, n, num_steps, flags);
+  A.R.out_dim = out_dim;
+  A.R.fin = finish_bound(*params);
+  A.n_member = n_member;
+  A.blocks_per_member = static_cast<int32_t>(grid_blocks(n_member, kQWsEnvs));
+  A.members = members;
+  for (int m = 0; m < members; ++m)
+    A.mem[m] = QMember{static_cast<const uint8_t*>(actors[m].net),
+                       opponent_mode == 3 ? static_cast<const uint8_t*>(actors[m].opp_net) : nullptr, actors[m].seed,
+                       actors[m].greedy_threshold, actors[m].opp_greedy_threshold};
+  const bool checked = out_dim > MG_NUM_ACTIONS;
+  void (*const kernel)(QRolloutMany) =
+      opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true, true> : qnet_rollout_ws_kernel<0, false, true>)
+      : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true, true> : qnet_rollout_ws_kernel<1, false, true>)
+      : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true, true>
+                           : qnet_rollout_ws_kernel<3, true, true>;
+  launch(kernel, static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kQWsThreads,
+         static_cast<hipStream_t>(stream), A);
+  return finish_launch("mg_rollout_qnet_many");
+}
+
 int mg_rollout_hdqn(const mg_params* params, const mg_state* state, const mg_traj* traj,
                     const mg_hdqn_traj* htraj, const mg_stats* stats, int8_t* goal, int8_t* goal_op,
                     double* ext_acc, int64_t n, int64_t env_offset, uint64_t seed, uint64_t first_step,
@@ -346,6 +402,76 @@ int mg_replay_store(float* rows, uint64_t* counter, int64_t capacity, int32_t ro
   hipLaunchKernelGGL(write_kernel, dim3(static_cast<unsigned>(nbx), chunks), dim3(kRBlock), 0, st, R, S, counter,
                      rows, capacity);
   return finish_launch("mg_replay_store");
+}
+
+size_t mg_replay_scratch_many_bytes(int64_t n_member, int32_t num_steps, int32_t members) {
+  if (members < 1 || members > 64) return 0;
+  return static_cast<size_t>(members) * mg_replay_scratch_bytes(n_member, num_steps);
+}
+
+int mg_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                         int32_t row_floats, const mg_transitions* tr, int64_t n_member, int32_t num_steps,
+                         int32_t skip_ego_won, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* const who = "mg_replay_store_many: %s";
+  if (members < 1 || members > 64) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
+  if (!rows || !counters || !tr) return fail(hipErrorInvalidValue, who, "NULL pointer");
+  for (int m = 0; m < members; ++m) {
+    if (!rows[m] || !counters[m]) return fail(hipErrorInvalidValue, who, "NULL pointer (a member's rows or counter)");
+    if (misaligned(rows[m], 7) || misaligned(counters[m], 7))
+      return fail(hipErrorInvalidValue, who, "every member's rows and counter must be 8-byte aligned");
+    for (int k = 0; k < m; ++k)
+      if (rows[k] == rows[m] || counters[k] == counters[m])
+        return fail(hipErrorInvalidValue, who,
+                    "a ring is listed twice (two members' appends to one ring have no defined order)");
+  }
+  if (capacity < 1) return fail(hipErrorInvalidValue, who, "capacity < 1");
+  if (row_floats != kRow || tr->goal || tr->next_goal || tr->meta_goal)
+    return fail(hipErrorInvalidValue, who, "22-float rows only: row_floats must be 22 and goal, next_goal, meta_goal NULL");
+  if (n_member < 0 || num_steps < 0) return fail(hipErrorInvalidValue, who, "n_member < 0 or num_steps < 0");
+  if (n_member % 64 != 0)
+    return fail(hipErrorInvalidValue, who,
+                "n_member must be a multiple of 64 (a member's won bits begin a word of the mask)");
+  if (n_member == 0 || num_steps == 0) return 0;
+  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
+    return fail(hipErrorInvalidValue, who, "obs_first, obs, a1 (or flags) and rew are required");
+  if (misaligned(tr->obs_first, 7) || misaligned(tr->obs, 7) || misaligned(tr->final_obs, 7) ||
+      misaligned(tr->rew, 7) || misaligned(tr->won_mask, 7) || misaligned(scratch, 7))
+    return fail(hipErrorInvalidValue, who, "float buffers, won_mask and scratch must be 8-byte aligned");
+  if (misaligned(tr->reward, 3)) return fail(hipErrorInvalidValue, who, "reward must be 4-byte aligned");
+  const int64_t nbx = (n_member + kRBlock - 1) / kRBlock;
+  const int64_t nb = nbx * num_steps;
+  if (nbx > 0x7fffffff || replay_groups(nb) > 0x7fffffff)
+    return fail(hipErrorInvalidValue, who, "n_member * num_steps exceeds the grid limit");
+  if (!scratch || scratch_bytes < mg_replay_scratch_many_bytes(n_member, num_steps, members))
+    return fail(hipErrorInvalidValue, who,
+                "scratch smaller than mg_replay_scratch_many_bytes(n_member, num_steps, members)");
+  const unsigned chunks = static_cast<unsigned>((num_steps + kRTChunk - 1) / kRTChunk);
+  if (chunks > 65535) return fail(hipErrorInvalidValue, who, "num_steps too large");
+  ReplayMany A{};
+  A.X = *tr;
+  A.n = n_member;
+  A.N = n_member * members;
+  A.words = (A.N + 63) >> 6;
+  A.nbx = nbx;
+  A.nb = nb;
+  A.T = num_steps;
+  A.skip_won = skip_ego_won;
+  A.scratch_stride = static_cast<int64_t>(mg_replay_scratch_bytes(n_member, num_steps));
+  A.scratch = static_cast<uint8_t*>(scratch);
+  A.cap = capacity;
+  A.ng = replay_groups(nb);
+  for (int m = 0; m < members; ++m) {
+    A.ring[m] = rows[m];
+    A.counter[m] = counters[m];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned M = static_cast<unsigned>(members);
+  hipLaunchKernelGGL(replay_scan_many_kernel, dim3(static_cast<unsigned>(A.ng), M), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(replay_group_scan_many_kernel, dim3(M), dim3(64), 0, st, A);
+  // the member instance reads ring, counter and scratch from A: its other four arguments are unused
+  hipLaunchKernelGGL((replay_write_kernel<0, true>), dim3(static_cast<unsigned>(nbx), chunks, M), dim3(kRBlock), 0, st,
+                     A, ReplayScratch{}, static_cast<const uint64_t*>(nullptr), static_cast<float*>(nullptr), int64_t{0});
+  return finish_launch("mg_replay_store_many");
 }
 
 int mg_replay_sample(const float* rows, const uint64_t* counter, int64_t capacity,

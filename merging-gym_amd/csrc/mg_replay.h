@@ -1,6 +1,9 @@
-// mg_replay.h -- the DQN replay ring: ReplayIn, ReplayScratch, the scan, write and sample kernels, counter_add_kernel.
+// mg_replay.h -- the DQN replay ring: ReplayIn, ReplayScratch, the scan, write and sample kernels, counter_add_kernel,
+// and the store with the member in the grid (ReplayMany).
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
+
+#include <type_traits>
 
 #include "mg_common.h"
 #include "mg_env.h"
@@ -37,6 +40,10 @@ struct ReplayIn {
   int64_t nb;     // nbx * T
   int32_t T;
   int32_t skip_won;
+  // n is the live limit of a column index and, here, also the row stride of the [T, n, ...] tensors, whose
+  // first column is this batch's (ReplayMany: a member's slice of a wider batch)
+  __device__ int64_t stride() const { return n; }
+  __device__ int64_t col0() const { return 0; }
 };
 
 struct ReplayScratch {  // carved from the caller's scratch buffer (8-byte header reserved)
@@ -56,19 +63,20 @@ __host__ __device__ inline ReplayScratch replay_scratch(void* base, int64_t nb) 
   return S;
 }
 
-__device__ __forceinline__ bool replay_keep(const ReplayIn& R, int t, int64_t i) {
+// col0: the batch's first column in the tensors (a multiple of 64; 0 but for a member's slice)
+__device__ __forceinline__ bool replay_keep(const ReplayIn& R, int t, int64_t i, int64_t col0 = 0) {
   if (i >= R.n) return false;
   if (!R.skip_won || R.X.won_mask == nullptr) return true;
-  const uint64_t w = R.X.won_mask[static_cast<int64_t>(t) * R.words + (i >> 6)];
+  const uint64_t w = R.X.won_mask[static_cast<int64_t>(t) * R.words + ((col0 + i) >> 6)];
   return ((w >> (i & 63)) & 1u) == 0;
 }
 
 // Kept transitions of write block (t, bx).
-__device__ __forceinline__ uint32_t replay_block_count(const ReplayIn& R, int t, int64_t bx) {
+__device__ __forceinline__ uint32_t replay_block_count(const ReplayIn& R, int t, int64_t bx, int64_t col0 = 0) {
   const int64_t i0 = bx * kRBlock;
   const int64_t live = R.n - i0 < kRBlock ? R.n - i0 : kRBlock;
   if (!R.skip_won || R.X.won_mask == nullptr) return static_cast<uint32_t>(live);
-  const uint64_t* w = R.X.won_mask + static_cast<int64_t>(t) * R.words + (i0 >> 6);
+  const uint64_t* w = R.X.won_mask + static_cast<int64_t>(t) * R.words + ((col0 + i0) >> 6);
   uint64_t wk[kRBlock / 64];
 #pragma unroll
   for (int k = 0; k < kRBlock / 64; ++k) wk[k] = live > 64 * k ? w[k] : ~0ull;  // loads issued together
@@ -121,14 +129,20 @@ __global__ __launch_bounds__(64) void replay_group_scan_kernel(const ReplayScrat
   replay_group_scan(S, ng, counter);
 }
 
-__global__ __launch_bounds__(64) void replay_scan_kernel(const ReplayIn R, ReplayScratch S) {
+// One wave: the keep counts of group g's write blocks, their in-group offsets, the group's total.
+__device__ __forceinline__ void replay_scan_group(const ReplayIn& R, const ReplayScratch& S, unsigned g,
+                                                  int64_t col0 = 0) {
   const int lane = threadIdx.x;
-  const int64_t b = static_cast<int64_t>(blockIdx.x) * kRGroup + lane;
+  const int64_t b = static_cast<int64_t>(g) * kRGroup + lane;
   uint32_t c = 0;
-  if (b < R.nb) c = replay_block_count(R, static_cast<int>(b / R.nbx), b % R.nbx);
+  if (b < R.nb) c = replay_block_count(R, static_cast<int>(b / R.nbx), b % R.nbx, col0);
   const uint32_t incl = wave_incl_scan(c);
   if (b < R.nb) S.local[b] = incl - c;
-  if (lane == 63) S.group_total[blockIdx.x] = incl;
+  if (lane == 63) S.group_total[g] = incl;
+}
+
+__global__ __launch_bounds__(64) void replay_scan_kernel(const ReplayIn R, ReplayScratch S) {
+  replay_scan_group(R, S, blockIdx.x);
 }
 
 // Rank of the calling thread among the block's kept threads, and the block total.
@@ -158,13 +172,63 @@ __device__ __forceinline__ void load_row10(const float* src, float (&v)[kObs]) {
   }
 }
 
+// ---- the member in the grid (mg_replay_store_many): member m's slice [m n_member, (m + 1) n_member) of one
+// [T, N, ...] batch into ring m, as mg_replay_store would store a contiguous copy of the slice. A block's
+// column index i stays local to its member (live while i < n = n_member; write blocks, scan groups and ring
+// positions are per member); the tensors are addressed at column col0() + i with the batch's row stride N
+// and its ceil(N / 64) won-mask words per step. n_member is a multiple of 64, so a member's won bits begin
+// a word. 22-float rows (KIND 0) only. The member is the grid's last dimension.
+struct ReplayMany : ReplayIn {  // X: the whole batch; n = n_member; words = ceil(N / 64); nbx, nb: per member
+  int64_t N;               // the batch's envs, the row stride
+  int64_t scratch_stride;  // bytes of one member's scratch
+  uint8_t* scratch;
+  int64_t cap;
+  int64_t ng;              // replay_groups(nb)
+  float* ring[64];
+  uint64_t* counter[64];
+  __device__ int64_t stride() const { return N; }
+  __device__ int64_t col0() const { return static_cast<int64_t>(blockIdx.z) * n; }  // the write kernel's grid
+  __device__ ReplayScratch member_scratch(int m) const {
+    return replay_scratch(scratch + static_cast<int64_t>(m) * scratch_stride, nb);
+  }
+};
+static_assert(sizeof(ReplayMany) <= 4096, "HIP's kernel argument limit");
+
+// What a block of replay_write_kernel takes from its other arguments (lone), or from its member's entries.
+__device__ __forceinline__ const ReplayScratch& replay_view_scratch(const ReplayIn&, const ReplayScratch& S) { return S; }
+__device__ __forceinline__ const uint64_t* replay_view_counter(const ReplayIn&, const uint64_t* c) { return c; }
+__device__ __forceinline__ float* replay_view_rows(const ReplayIn&, float* rows) { return rows; }
+__device__ __forceinline__ int64_t replay_view_cap(const ReplayIn&, int64_t cap) { return cap; }
+__device__ __forceinline__ ReplayScratch replay_view_scratch(const ReplayMany& A, const ReplayScratch&) {
+  return A.member_scratch(blockIdx.z);
+}
+__device__ __forceinline__ const uint64_t* replay_view_counter(const ReplayMany& A, const uint64_t*) {
+  return A.counter[blockIdx.z];
+}
+__device__ __forceinline__ float* replay_view_rows(const ReplayMany& A, float*) { return A.ring[blockIdx.z]; }
+__device__ __forceinline__ int64_t replay_view_cap(const ReplayMany& A, int64_t) { return A.cap; }
+
+__global__ __launch_bounds__(64) void replay_scan_many_kernel(const ReplayMany A) {  // grid (groups, members)
+  replay_scan_group(A, A.member_scratch(blockIdx.y), blockIdx.x, static_cast<int64_t>(blockIdx.y) * A.n);
+}
+
+__global__ __launch_bounds__(64) void replay_group_scan_many_kernel(const ReplayMany A) {  // grid (members)
+  replay_group_scan(A.member_scratch(blockIdx.x), A.ng, A.counter[blockIdx.x]);
+}
+
 // KIND 0: main.py's DQN rows [s, a, r, s']; 1: hdqn.py's lower-level goal rows
 // [goal, s, a, r, next_goal, s']; 2: Goal_DQN's rows [s', meta_goal, r, s'] (hdqn.py:97-101 at
 // :325, where state is already next_state).
-template <int KIND>
-__global__ __launch_bounds__(kRBlock) void replay_write_kernel(const ReplayIn R, const ReplayScratch S,
-                                                               const uint64_t* counter, float* rows,
-                                                               int64_t cap) {
+// MANY: the member in the grid (mg_replay_store_many; ReplayMany above) -- grid (write blocks, chunks, members),
+// the first argument a ReplayMany and the other four unused: ring, counter and scratch are member blockIdx.z's.
+template <int KIND, bool MANY = false>
+__global__ __launch_bounds__(kRBlock) void replay_write_kernel(const std::conditional_t<MANY, ReplayMany, ReplayIn> R,
+                                                               const ReplayScratch S1, const uint64_t* counter1,
+                                                               float* rows1, int64_t cap1) {
+  decltype(auto) S = replay_view_scratch(R, S1);
+  const uint64_t* counter = replay_view_counter(R, counter1);
+  float* rows = replay_view_rows(R, rows1);
+  const int64_t cap = replay_view_cap(R, cap1);
   constexpr bool GOAL = KIND == 1;
   constexpr bool META = KIND == 2;
   constexpr int kRow = GOAL ? kRowGoal : 2 * kObs + 2;  // floats per row
@@ -175,6 +239,7 @@ __global__ __launch_bounds__(kRBlock) void replay_write_kernel(const ReplayIn R,
   const int64_t bx = blockIdx.x;
   const int64_t i = bx * kRBlock + threadIdx.x;
   const bool live = i < R.n;
+  const int64_t c = R.col0() + i;  // the column in the tensors
   const int t0 = blockIdx.y * kRTChunk;
   const int t1 = t0 + kRTChunk < R.T ? t0 + kRTChunk : R.T;
   const uint64_t end = *counter;  // memory_counter after this whole store
@@ -183,14 +248,14 @@ __global__ __launch_bounds__(kRBlock) void replay_write_kernel(const ReplayIn R,
   const uint64_t first = end > static_cast<uint64_t>(cap) ? end - static_cast<uint64_t>(cap) : 0u;
   float s[kObs], o[kObs];
   if (live) {
-    load_row10(t0 == 0 ? R.X.obs_first + i * kObs : R.X.obs + ((t0 - 1) * R.n + i) * kObs, s);
-    load_row10(R.X.obs + (t0 * R.n + i) * kObs, o);
+    load_row10(t0 == 0 ? R.X.obs_first + c * kObs : R.X.obs + ((t0 - 1) * R.stride() + c) * kObs, s);
+    load_row10(R.X.obs + (t0 * R.stride() + c) * kObs, o);
   }
   for (int t = t0; t < t1; ++t) {
-    const int64_t row = static_cast<int64_t>(t) * R.n + i;
-    const bool keep = replay_keep(R, t, i);
+    const int64_t row = static_cast<int64_t>(t) * R.stride() + c;
+    const bool keep = replay_keep(R, t, i, R.col0());
     float on[kObs];  // next step's row in flight while this step is gathered and written
-    if (live && t + 1 < t1) load_row10(R.X.obs + (row + R.n) * kObs, on);
+    if (live && t + 1 < t1) load_row10(R.X.obs + (row + R.stride()) * kObs, on);
     int total;
     const int rank = block_rank(keep, wave_cnt, total);
     if (total > 0) {  // uniform across the block

@@ -1,6 +1,9 @@
-// mg_rollout_qnet.h -- config 5, the Q-net policy rollout: FinishBound, QRollout, qnet_rollout_ws_kernel.
+// mg_rollout_qnet.h -- config 5, the Q-net policy rollout: FinishBound, QRollout, qnet_rollout_ws_kernel, and
+// the same kernel with the member in the grid (QRolloutMany, QMemberRollout, the MANY instances).
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
+
+#include <type_traits>
 
 #include "mg_common.h"
 #include "mg_env.h"
@@ -103,6 +106,53 @@ struct QRollout {
   int32_t out_dim;
   uint32_t flags;
   FinishBound fin;  // may_finish_next's constants
+  // n is the row stride of every [T, n, ...] output; end() is where the envs this block may touch stop
+  // (the same number here; a member's slice end in QMemberRollout)
+  __device__ int64_t end() const { return n; }
+};
+
+// ---- the member in the grid (mg_rollout_qnet_many; the kernel's MANY instances): one batch of members * n_member envs, member m
+// owning envs [m n_member, (m + 1) n_member) and acting with its own net, opponent net, seed and
+// thresholds. The kernel argument carries the shared launch and the members' scalars.
+constexpr int kQMaxMembers = 64;
+struct QMember {
+  const uint8_t* net;
+  const uint8_t* opp_net;
+  uint64_t seed;
+  uint64_t greedy_thr;
+  uint64_t opp_greedy_thr;
+};
+struct QRolloutMany {
+  QRollout R;        // shared: n = members * n_member (the row stride); net, seed, thresholds unused
+  int64_t n_member;  // a multiple of 64: no won-mask word spans two members
+  int32_t blocks_per_member;  // ceil(n_member / kQWsEnvs)
+  int32_t members;
+  QMember mem[kQMaxMembers];
+};
+static_assert(sizeof(QRolloutMany) <= 4096, "HIP's kernel argument limit");
+
+// What the role functions see of a member's block: the shared launch by reference (the kernel
+// argument, never copied) and the member's own scalars, block-uniform. Field for field QRollout's names.
+struct QMemberRollout {
+  const mg_params& P;
+  const Reset0& R0;
+  const mg_state& S;
+  const mg_traj& T;
+  const mg_stats& St;
+  const uint8_t* net;
+  const uint8_t* opp_net;
+  uint64_t seed;
+  uint64_t first_step;
+  uint64_t greedy_thr;
+  uint64_t opp_greedy_thr;
+  int64_t env_offset;
+  int64_t n;    // row stride: the whole batch
+  int64_t lim;  // the member's end, (m + 1) n_member
+  int32_t num_steps;
+  int32_t out_dim;
+  uint32_t flags;
+  const FinishBound& fin;
+  __device__ int64_t end() const { return lim; }
 };
 
 // Whether env e's next step can end its episode, for ANY pair of actions (a conservative superset of
@@ -137,7 +187,8 @@ MG_HD bool may_finish_next(const mg_params& P, const Env& e, const obs_t (&o)[kO
 // The need bits of env gi's step `step` for the config-5 Q-net waves (opponent modes 2 / 3): bit 0
 // the ego's forward (its greedy draw, or may_finish_next while statistics are kept), bit 1 the
 // opponent's (its greedy draw). u: the step's Philox words (qnet_policy_step_n's stream).
-__device__ __forceinline__ uint8_t qnet_need_bits(const QRollout& R, const uint4& u, bool live, const Env& e,
+template <class RT>
+__device__ __forceinline__ uint8_t qnet_need_bits(const RT& R, const uint4& u, bool live, const Env& e,
                                                   const obs_t (&o)[kObs]) {
   if (!live) return 0;
   const bool fin = R.St.rec != nullptr && (R.flags & MG_AUTORESET) && may_finish_next(R.P, e, o, R.fin);
@@ -182,8 +233,8 @@ __device__ __forceinline__ void put_q_row(float* row, const float (&q)[8]) {
 // net with out_dim > 5) gets env_step's KeyError semantics (env_step_lockstep).
 // qrow: the tile row of env i0 (rows of envs i0 + 64 j follow 64 rows apart), where the Q-net wave
 // left eval_net(state)[0..4] of the state the step acts on: a finishing env logs q[a1] (main.py:221).
-template <int OPP, int N, bool CHECKED>
-__device__ __forceinline__ void qnet_policy_step_n(const QRollout& R, Env (&e)[N], StepOut (&r)[N],
+template <int OPP, int N, bool CHECKED, class RT>
+__device__ __forceinline__ void qnet_policy_step_n(const RT& R, Env (&e)[N], StepOut (&r)[N],
                                                    int64_t i0, const bool (&live)[N], int t,
                                                    const int (&greedy1)[N], const int (&greedy2)[N],
                                                    bool (&won)[N], const float* qrow, uint2 (&keep)[N],
@@ -254,10 +305,11 @@ __device__ __forceinline__ void qnet_policy_step_n(const QRollout& R, Env (&e)[N
 }
 
 // Observation of env i (or zeros past n) into its fp32 tile row; returns live.
-__device__ __forceinline__ bool qnet_load_env(const QRollout& R, int64_t i, Env& e, float* row) {
+template <class RT>
+__device__ __forceinline__ bool qnet_load_env(const RT& R, int64_t i, Env& e, float* row) {
   const mg_params& P = R.P;
   double o[kObs];
-  const bool live = i < R.n;
+  const bool live = i < R.end();
   if (live) {
     e = load_env(R.S, i);
     double x1, y1, x2, y2;
@@ -330,7 +382,8 @@ __device__ __forceinline__ void qws2_put(const float (&q)[8], int out_dim, bool 
 // The wave's 128 envs of the group are compacted by their need bits into one list, the opponent's
 // items (swapped view) first, and run through the forward 64 at a time on col_tiles(count) column
 // tiles. list / stage / qt: this wave's qlist, qstage ([h][item]) and qtail.
-__device__ __forceinline__ void qws_q_selfplay(const QRollout& R, const uint8_t* lds_net, float* tile,
+template <class RT>
+__device__ __forceinline__ void qws_q_selfplay(const RT& R, const uint8_t* lds_net, float* tile,
                                                uint8_t* greedy0, uint8_t* greedy1, uint8_t* list, u32x4* stage,
                                                int (&qt)[4], int p) {
   static_assert(kQWsTiles == 2, "the list holds the wave's two 64-env tiles");
@@ -415,7 +468,8 @@ __device__ __forceinline__ void qws3_put(const float (&q)[8], int out_dim, bool 
 // only (an episode can end only there, main.py:221) and only once the opponent wave of the same
 // rows has read them: that wave lists those items first and publishes the phase in qrows_read[hw]
 // after their forward; the ego wave lists them last.
-__device__ __forceinline__ void qws_q_split(const QRollout& R, const uint8_t* lds_net, const uint8_t* lds_net2,
+template <class RT>
+__device__ __forceinline__ void qws_q_split(const RT& R, const uint8_t* lds_net, const uint8_t* lds_net2,
                                             float* tile, uint8_t* greedy0, uint8_t* greedy1, uint8_t* list,
                                             int (&qt)[4], int* qrows_read, int p) {
   static_assert(kQWsHalf == 512, "two waves per net, 256 envs each");
@@ -482,8 +536,8 @@ __device__ __forceinline__ void qws_q_split(const QRollout& R, const uint8_t* ld
 
 // OPP 2 / 3, env wave ew: Q-net wave ew's list tail for Q(group p & 1, step p / 2) -- its 1..16
 // items past three full forwards, one column tile -- as that wave would run it (qtail).
-template <int OPP>
-__device__ __forceinline__ void qws_env_tail(const QRollout& R, const uint8_t* lds_net, const uint8_t* lds_net2,
+template <int OPP, class RT>
+__device__ __forceinline__ void qws_env_tail(const RT& R, const uint8_t* lds_net, const uint8_t* lds_net2,
                                              float* tile, uint8_t* greedy0, uint8_t* greedy1, const uint8_t* list,
                                              const u32x4* stage, const int (&qt)[4], int* qrows_read, int p, int ew) {
   qws_wait(&qt[0], p);
@@ -510,11 +564,44 @@ __device__ __forceinline__ void qws_env_tail(const QRollout& R, const uint8_t* l
   }
 }
 
+// What a block of the kernel below works on, lone (the launch itself, envs from kQWsEnvs blockIdx.x) and
+// with the member in the grid (the member's view, envs from its slice's start).
+__device__ __forceinline__ const QRollout& qws_block_view(const QRollout& R) { return R; }
+__device__ __forceinline__ int64_t qws_block_base(const QRollout&) {
+  return static_cast<int64_t>(blockIdx.x) * kQWsEnvs;
+}
+__device__ __forceinline__ int qws_member(const QRolloutMany& A) {
+  return static_cast<int>(blockIdx.x) / A.blocks_per_member;
+}
+__device__ __forceinline__ QMemberRollout qws_block_view(const QRolloutMany& A) {
+  const int m = qws_member(A);
+  const QMember& me = A.mem[m];
+  return QMemberRollout{A.R.P,          A.R.R0,          A.R.S,          A.R.T,
+                        A.R.St,         me.net,          me.opp_net,     me.seed,
+                        A.R.first_step, me.greedy_thr,   me.opp_greedy_thr, A.R.env_offset,
+                        A.R.n,          (m + 1) * A.n_member, A.R.num_steps, A.R.out_dim,
+                        A.R.flags,      A.R.fin};
+}
+__device__ __forceinline__ int64_t qws_block_base(const QRolloutMany& A) {
+  const int m = qws_member(A);
+  const int local = static_cast<int>(blockIdx.x) - m * A.blocks_per_member;
+  return m * A.n_member + static_cast<int64_t>(local) * kQWsEnvs;
+}
+
 // CHECKED: a greedy action may fall outside action_dict (a net with out_dim > 5): the lockstep step
 // carries the KeyError selects. Every other launch takes CHECKED = false (-2 % on the ego-only
 // leg, r03i; the self-play and other-net instances showed no gain and keep the checked step).
-template <int OPP, bool CHECKED>
-__global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws_kernel(const QRollout R) {
+// MANY: the member in the grid (mg_rollout_qnet_many, below) -- the same block on a member's slice of a
+// wider batch. Block b is then local block b mod blocks_per_member of member b div blocks_per_member, its
+// first env m n_member + kQWsEnvs local -- off the kQWsEnvs grid whenever n_member is no multiple of it,
+// so a member's last block ends at the member's end (R.end()), not the batch's. Rows stride by the whole
+// batch (R.n); the Philox env index stays env_offset + i, i within the batch, so member m is a lone launch
+// on n_member envs at env_offset + m n_member. The member's scalars are block-uniform: read once from the
+// kernel argument by a uniform index (scalar loads).
+template <int OPP, bool CHECKED, bool MANY = false>
+__global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws_kernel(
+    const std::conditional_t<MANY, QRolloutMany, QRollout> A) {
+  decltype(auto) R = qws_block_view(A);  // QRollout itself, or the member's QMemberRollout
   constexpr int kIlp = kQWsIlp;
   constexpr int kEnvs = kQWsEnvs;  // envs per block
   constexpr int kHalf = kQWsHalf;  // envs per group
@@ -545,7 +632,7 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
   __shared__ int qtail[OPP >= 2 ? 4 : 1][4];
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kEnvs;
+  const int64_t base = qws_block_base(A);
   const int ew = wave - 4;
 
   if constexpr (kNet32) {
@@ -641,11 +728,11 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
       const int64_t wbase = base + local0;
 #pragma unroll
       for (int j = 0; j < kIlp; ++j) {
-        const int64_t rem = R.n - (wbase + 64 * j);
+        const int64_t rem = R.end() - (wbase + 64 * j);
         store_won_mask(R.T.won_mask, won[j], t, R.n, wbase + 64 * j,
                        rem <= 0 ? 0 : (rem < 64 ? static_cast<int>(rem) : 64));
       }
-      const int64_t wrem = R.n - wbase;
+      const int64_t wrem = R.end() - wbase;
       const int wrows = wrem <= 0 ? 0 : (wrem < 64 * kIlp ? static_cast<int>(wrem) : 64 * kIlp);
       wave_store_obs_n<kIlp>(tile + local0 * kObs, r,
                              R.T.obs ? R.T.obs + (static_cast<int64_t>(t) * R.n + wbase) * kObs : nullptr,

@@ -80,6 +80,13 @@ class DqnMember(_c.Structure):
                 ("first_draw", _c.c_uint64), ("hyper", DqnHyper)]
 
 
+class QnetActor(_c.Structure):
+    """struct mg_qnet_actor: one member of mg_rollout_qnet_many -- its packed net, its opponent's (mode 3), its
+    seed and its two greedy thresholds."""
+    _fields_ = [("net", _P), ("opp_net", _P), ("seed", _c.c_uint64), ("greedy_threshold", _c.c_uint64),
+                ("opp_greedy_threshold", _c.c_uint64)]
+
+
 class Stats(_c.Structure):
     _fields_ = [("rec", _P)]  # mg_episode_stats [n] (64 bytes each, see EPISODE_STATS_DTYPE)
 
@@ -189,6 +196,17 @@ def _load(path=LIB_PATH):
     lib.mg_dqn_learn_many.argtypes = [_P, _P, _c.c_size_t] + many_args + [_P, _c.c_size_t, _P, _c.c_size_t, _P]
     lib.mg_host_dqn_learn_many.argtypes = [_P] + many_args + [_P, _c.c_size_t]
     for f in (lib.mg_dqn_learn_many_init, lib.mg_dqn_learn_many, lib.mg_host_dqn_learn_many):
+        f.restype = _c.c_int
+    # a population acting (additive to ABI 21): the members' rollouts in one launch, their stores in three
+    lib.mg_rollout_qnet_many.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _c.c_int64,
+                                         _c.c_uint64, _c.c_int32, _c.POINTER(QnetActor), _c.c_int32, _c.c_int32,
+                                         _c.c_uint32, _P]
+    lib.mg_replay_scratch_many_bytes.argtypes = [_c.c_int64, _c.c_int32, _c.c_int32]
+    lib.mg_replay_scratch_many_bytes.restype = _c.c_size_t
+    lib.mg_replay_store_many.argtypes = [_c.POINTER(_P), _c.POINTER(_P), _c.c_int32, _c.c_int64, _c.c_int32,
+                                         _c.POINTER(Transitions), _c.c_int64, _c.c_int32, _c.c_int32, _P,
+                                         _c.c_size_t, _P]
+    for f in (lib.mg_rollout_qnet_many, lib.mg_replay_store_many):
         f.restype = _c.c_int
     # Rainbow acting (additive to ABI 21): the packed net, its forward, the fused rollout, the host head
     lib.mg_rainbow_packed_bytes.restype = _c.c_size_t

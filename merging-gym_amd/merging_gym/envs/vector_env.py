@@ -368,6 +368,72 @@ class MergeVecEnv:
         self._step_idx = k0 + T
         return buf["_result"]
 
+    def rollout_qnet_many(self, num_steps: int, qnets, seed, opponent="none", episilo=0.7, opp_episilo=0.7,
+                          first_step=None, final_observation: bool = True, won_mask: bool = True):
+        """rollout_qnet for M actors in ONE launch: qnets is a list of M QNets of one out_dim, and member m owns
+        envs [m n, (m + 1) n), n = num_envs / M (a multiple of 64: a won-mask word never spans two members),
+        where it acts with qnets[m]. seed, episilo and opp_episilo are each one value or a sequence of M.
+        opponent: "none", "uniform" or "self" for every member, or a list of M QNets -- member m's own opponent
+        net, which may be another member's qnets[j] (cross-play) or a frozen checkpoint. The Philox env index
+        is this env's env_offset + i, so member m's slice is bit for bit what a lone
+        MergeVecEnv(n, env_offset=self.env_offset + m n) holding the slice's state gives for
+        rollout_qnet(num_steps, qnets[m], seed[m], ...). Returns the same [T, N, ...] dict as rollout_qnet
+        (replay.store_rollout_many appends it to M rings in place). The members' scalars travel in the kernel
+        argument: a call allocates and synchronises nothing."""
+        from ..policy import greedy_threshold
+        from ..population import MAX_MEMBERS, _per_member
+
+        nat = self._nat
+        qnets = list(qnets)
+        M, T = len(qnets), int(num_steps)
+        if not 1 <= M <= MAX_MEMBERS:
+            raise ValueError(f"rollout_qnet_many takes 1..{MAX_MEMBERS} nets, got {M}")
+        if self.num_envs % M or (self.num_envs // M) % 64:
+            raise ValueError(f"num_envs = {self.num_envs} must be {M} slices of a multiple of 64 envs (a won-mask "
+                             "word covers 64 envs, so two members must not share one)")
+        out_dim = qnets[0].out_dim
+        if any(q.out_dim != out_dim for q in qnets):
+            raise ValueError("the nets of one launch share one out_dim")
+        if any(q.in_dim != _OBS_DIM for q in qnets):
+            raise ValueError("the fused rollout feeds the 10-value observation: the nets need in_dim 10")
+        opp_nets = [None] * M
+        if isinstance(opponent, str):
+            mode = {"none": 0, "uniform": 1, "self": 2}[opponent]
+        else:  # each member's own opponent net
+            mode, opp_nets = 3, list(opponent)
+            if len(opp_nets) != M:
+                raise ValueError(f"opponent: expected a mode or {M} nets, got {len(opp_nets)}")
+            if any(o.in_dim != _OBS_DIM or o.out_dim != out_dim for o in opp_nets):
+                raise ValueError("the opponents' nets need in_dim 10 and the ego nets' out_dim")
+        seeds = _per_member(seed, M, "seed")
+        eps, opp_eps = _per_member(episilo, M, "episilo"), _per_member(opp_episilo, M, "opp_episilo")
+        actors = (nat.QnetActor * M)()
+        for m in range(M):
+            actors[m] = nat.QnetActor(qnets[m].packed.data_ptr(),
+                                      None if opp_nets[m] is None else opp_nets[m].packed.data_ptr(),
+                                      int(seeds[m]) & U64, greedy_threshold(eps[m]), greedy_threshold(opp_eps[m]))
+        k0 = self._step_idx if first_step is None else int(first_step)
+        buf = self._traj(T, final_observation, won_mask)
+        rc = nat.lib.mg_rollout_qnet_many(
+            self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, self.num_envs // M, M,
+            self.env_offset, k0 & U64, T, actors, out_dim, mode, self._flags, self._stream())
+        nat.check(rc, "mg_rollout_qnet_many")
+        self._step_idx = k0 + T
+        return buf["_result"]
+
+    def member_summaries(self, members: int):
+        """episode_summary() of each of `members` equal slices of the batch (rollout_qnet_many's members): a
+        list of the summaries the lone envs holding those slices would give."""
+        from ..distributed import summarize
+
+        if self.returns is None:
+            raise ValueError("built with episode_stats=False")
+        M = int(members)
+        if M < 1 or self.num_envs % M:
+            raise ValueError(f"num_envs = {self.num_envs} is not {M} equal slices")
+        n = self.num_envs // M
+        return [summarize(self.returns[m * n:(m + 1) * n], self.counts[m * n:(m + 1) * n]) for m in range(M)]
+
     def rollout_rainbow(self, num_steps: int, net, opponent: str = "self", final_observation: bool = True,
                         won_mask: bool = True):
         """`num_steps` steps of ranbowdqn.py's acting loop (:662-680) in one launch: action =

@@ -8,9 +8,9 @@ ring, seed, counters and hyperparameters:
 
     rings = [ReplayRing(2000, device="cuda:0") for _ in range(8)]
     pop = DQNPopulation([sd] * 8, rings, lr=[0.01, 0.005, 0.02, 0.01, 0.01, 0.01, 0.01, 0.01], seed=range(8))
-    traj = envs[m].rollout_qnet(16, pop.qnets[m], seed)     # member m acts with its own net
-    rings[m].store_rollout(obs0, traj)
-    pop.learn(4)                                            # four updates of all eight members
+    env = MergeVecEnv(8 * 1024, device="cuda:0")            # member m owns envs [1024 m, 1024 (m + 1))
+    pop.collect(env, 16)                                    # every member acts with its own net and stores
+    pop.learn(4)                                            # into its own ring; four updates of all eight
     pop.copy_member(best, worst)                            # population-based training's exploit step
 
 Member m is bit for bit the lone DQNLearner built from the same net, ring, seed and hyperparameters:
@@ -123,6 +123,26 @@ class DQNPopulation(DQNNets):
     @property
     def seed(self):
         return [int(e.seed) for e in self._members]
+
+    # ------------------------------------------------------------------ act and store
+    def collect(self, env, num_steps: int, seed=None, opponent="none", episilo=0.7, opp_episilo=0.7,
+                skip_ego_won: bool = True):
+        """The acting half of the loop for every member at once: env.observe(), one
+        env.rollout_qnet_many(num_steps, self.qnets, ...) -- member m on its slice of env's batch -- and one
+        replay.store_rollout_many into self.rings: four launches beside the M rollouts and 3 M stores of the
+        members in turn, each member's slice, ring and counter bit for bit the lone loop's. seed: one value or
+        M (None: the members' own seeds); opponent, episilo, opp_episilo as rollout_qnet_many takes them.
+        Returns the trajectory. Refuses a population whose rings are shared."""
+        from .replay import store_rollout_many
+
+        if len({id(r) for r in self.rings}) != len(self.rings):
+            raise ValueError("collect() appends each member's transitions to its own ring: this population's "
+                             "rings are shared")
+        obs0 = env.observe()
+        traj = env.rollout_qnet_many(num_steps, self.qnets, self.seed if seed is None else seed, opponent, episilo,
+                                     opp_episilo)
+        store_rollout_many(self.rings, obs0, traj, skip_ego_won)
+        return traj
 
     # ------------------------------------------------------------------ learn
     def learn(self, num_updates: int = 1, filled_only: bool = False, return_loss: bool = False,

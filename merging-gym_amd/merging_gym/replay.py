@@ -201,3 +201,55 @@ class ReplayRing(RingBase):
         rows = self.sample_rows(batch_size, seed, draw, filled_only)
         k = _OBS_DIM + self._s0  # state width
         return (rows[:, :k], rows[:, k:k + 1].to(self._torch.int64), rows[:, k + 1:k + 2], rows[:, -k:])
+
+
+def store_rollout_many(rings, obs_first, traj, skip_ego_won: bool = True):
+    """Append one rollout of N = M n envs (MergeVecEnv.rollout_qnet_many's dict; obs_first [N, 10] = the
+    observation before step 0) to M rings, member m's slice [m n, (m + 1) n) to rings[m]: exactly what
+    rings[m].store_rollout leaves when given a contiguous copy of the slice, in three launches for all members
+    (mg_replay_store_many). The rings are plain (not goal), distinct, of one capacity and on one device; n is a
+    multiple of 64. traj["flags"] and traj["won_mask"] are read in place; like store_rollout it needs the
+    rollout's final_observation. Nothing is copied and nothing is synchronised."""
+    rings = list(rings)
+    M = len(rings)
+    if not 1 <= M <= 64:
+        raise ValueError(f"store_rollout_many takes 1..64 rings, got {M}")
+    r0 = rings[0]
+    torch = r0._torch
+    if any(r.goal for r in rings):
+        raise ValueError("the member store writes 22-float rows: goal rings are refused")
+    if any(r.capacity != r0.capacity or r.device != r0.device for r in rings):
+        raise ValueError("the rings share one capacity and one device")
+    if len({id(r) for r in rings}) != M:
+        raise ValueError("a ring is listed twice: two members' appends to one ring have no defined order")
+    final_obs = RingBase._final_observation(traj)
+    flags = traj.get("flags")
+    if flags is None or flags.dtype != torch.uint8 or flags.dim() != 3 or not flags.is_contiguous():
+        raise ValueError("the member store reads the rollout's interleaved [T, N, 4] uint8 flags buffer")
+    T, N = int(flags.shape[0]), int(flags.shape[1])
+    if N % M or (N // M) % 64:
+        raise ValueError(f"N = {N} must be {M} slices of a multiple of 64 envs")
+    obs_first = r0._f32(obs_first, (N, _OBS_DIM))
+    obs = r0._f32(traj["obs"], (T, N, _OBS_DIM))
+    rew = r0._f32(traj["rew"], (T, N, 2))
+    final_obs = r0._f32(final_obs, (T, N, _OBS_DIM))
+    won_mask = traj.get("won_mask")
+    if skip_ego_won:
+        if won_mask is None:
+            raise ValueError("skip_ego_won needs the rollout's won_mask (main.py:209): roll out with won_mask=True, "
+                             "or pass skip_ego_won=False")
+        if (won_mask.dtype != torch.int64 or tuple(won_mask.shape) != (T, (N + 63) // 64)
+                or not won_mask.is_contiguous() or won_mask.device != r0.device):
+            raise ValueError(f"won_mask must be a contiguous [{T}, {(N + 63) // 64}] int64 tensor on {r0.device}")
+    tr = _native.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), None, ptr(rew), None,
+                             ptr(won_mask) if skip_ego_won else None, None, None, None, ptr(flags), None)
+    need = int(_native.lib.mg_replay_scratch_many_bytes(N // M, T, M))
+    if r0._scratch.numel() * 8 < need:
+        r0._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=r0.device)
+    rows = (ctypes.c_void_p * M)(*(r.memory.data_ptr() for r in rings))
+    counters = (ctypes.c_void_p * M)(*(r._counter.data_ptr() for r in rings))
+    rc = _native.lib.mg_replay_store_many(rows, counters, M, r0.capacity, r0.row, ctypes.byref(tr), N // M, T,
+                                          1 if skip_ego_won else 0, r0._scratch.data_ptr(), r0._scratch.numel() * 8,
+                                          r0._stream())
+    _native.check(rc, "mg_replay_store_many")
+    r0._keepalive = (obs_first, obs, rew, final_obs, won_mask, flags)
