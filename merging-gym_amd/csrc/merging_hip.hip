@@ -45,8 +45,9 @@
 #include "mg_learn_core.h"      // the fixed-order fp32 primitives both learners share, learn_bwd_kernel
 #include "mg_learn.h"           // DQN.learn, lone and population: the update kernels with the member in the grid,
                                 // their launch order, host twin and the drivers of a call
-#include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss: replay store, update kernels, host twin
-#include "mg_per.h"             // prioritized replay: the sum / min trees, store, sample, update, the weighted learner
+#include "mg_per.h"             // prioritized replay alone: the sum / min trees, pow, store, sample, update
+#include "mg_rainbow_learn.h"   // Rainbow's compute_td_loss, plain or prioritized: replay stores, update kernels,
+                                // the launch order, host twin and the drivers of a call
 #include "mg_rainbow_noise.h"   // the learner's noise factors drawn on the device: Philox, inverse normal CDF, host twin
 
 extern "C" {
@@ -772,13 +773,7 @@ int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, co
                             int32_t num_steps, void* stream) {
   if (int e = check_rainbow_store("mg_rainbow_replay_store", rows, counter, capacity, tr, n, num_steps)) return e;
   if (n == 0 || num_steps == 0) return 0;
-  RlStore R{};
-  R.X = *tr;
-  R.n = n;
-  R.total = n * num_steps;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+  rainbow_store(rows, counter, capacity, tr, n, num_steps, nullptr, 0.0, false, static_cast<hipStream_t>(stream));
   return finish_launch("mg_rainbow_replay_store");
 }
 
@@ -786,47 +781,30 @@ size_t mg_rainbow_learner_bytes(void) { return static_cast<size_t>(kRlLearner) *
 
 size_t mg_rainbow_learn_scratch_bytes(int32_t batch) {
   if (batch < 1 || batch > 1024) return 0;
-  return static_cast<size_t>(rl_scratch(batch).total) * sizeof(float);
+  return static_cast<size_t>(rl_scratch(batch, false).total) * sizeof(float);
 }
+
+// The four learners: the call as given, the check, one driver (the plain learner is the prioritized one without a
+// tree).
 
 int mg_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
                      int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
                      const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out, float* proj_out,
                      float* grads_out, void* packed_out, void* scratch, size_t scratch_bytes, void* stream) {
-  if (int e = check_rainbow_learn("mg_rainbow_learn", learner, rows, counter, capacity, batch, num_updates, hyper, noise,
-                                  loss_out, rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes))
-    return e;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
-  // the effective weights of the stored noise; every update's last launch leaves the next one's
-  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 0);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
-                             noise, loss_out, rows_out, proj_out, grads_out);
-    launch_rainbow_learn_update(L, st);
-  }
-  if (packed_out)  // the acting kernels' layout of the current model's effective weights, on the same stream
-    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st,
-                       rainbow_learn_tensors(learner, L.eff), static_cast<uint8_t*>(packed_out));
-  return finish_launch("mg_rainbow_learn");
+  RLearnCall C{learner, rows, counter, capacity, batch, num_updates, first_update, seed, first_draw, hyper, noise,
+               loss_out, rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes};
+  if (int e = check_rainbow_learn("mg_rainbow_learn", C)) return e;
+  return rainbow_learn_device("mg_rainbow_learn", C, static_cast<hipStream_t>(stream));
 }
 
 int mg_host_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
                           int32_t num_updates, uint64_t first_update, uint64_t seed, uint64_t first_draw,
                           const mg_dqn_hyper* hyper, const float* noise, float* loss_out, float* rows_out,
                           float* proj_out, float* grads_out, void* scratch, size_t scratch_bytes) {
-  if (int e = check_rainbow_learn("mg_host_rainbow_learn", learner, rows, counter, capacity, batch, num_updates, hyper,
-                                  noise, loss_out, rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes))
-    return e;
-  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
-  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
-                             noise, loss_out, rows_out, proj_out, grads_out);
-    host_rainbow_learn_update(L);
-  }
-  g_err[0] = '\0';
-  return 0;
+  RLearnCall C{learner, rows, counter, capacity, batch, num_updates, first_update, seed, first_draw, hyper, noise,
+               loss_out, rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes};
+  if (int e = check_rainbow_learn("mg_host_rainbow_learn", C)) return e;
+  return rainbow_learn_host(C);
 }
 
 int mg_host_rainbow_project(const float* next_dist, const float* reward, const float* done, const float* support,
@@ -883,14 +861,7 @@ int mg_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_tran
   if (int e = check_per_tree("mg_per_store", tree, tree_bytes, capacity)) return e;
   if (int e = check_per_alpha("mg_per_store", alpha)) return e;
   if (n == 0 || num_steps == 0) return 0;
-  RlStore R{};
-  R.X = *tr;
-  R.n = n;
-  R.total = n * num_steps;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
-  launch_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha, st);
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+  rainbow_store(rows, counter, capacity, tr, n, num_steps, tree, alpha, false, static_cast<hipStream_t>(stream));
   return finish_launch("mg_per_store");
 }
 
@@ -901,13 +872,7 @@ int mg_host_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg
   if (int e = check_per_alpha("mg_host_per_store", alpha)) return e;
   g_err[0] = '\0';
   if (n == 0 || num_steps == 0) return 0;
-  RlStore R{};
-  R.X = *tr;
-  R.n = n;
-  R.total = n * num_steps;
-  for (int64_t i = 0; i < R.total; ++i) rl_store_at(R, counter, rows, capacity, i);
-  host_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha);
-  *counter += static_cast<uint64_t>(R.total);
+  rainbow_store(rows, counter, capacity, tr, n, num_steps, tree, alpha, true, nullptr);
   return 0;
 }
 
@@ -972,7 +937,7 @@ int mg_host_per_pow(const double* x, const double* y, double* out, int64_t n) {
 
 size_t mg_rainbow_learn_prioritized_scratch_bytes(int32_t batch) {
   if (batch < 1 || batch > 1024) return 0;
-  return static_cast<size_t>(per_scratch(batch).total) * sizeof(float);
+  return static_cast<size_t>(rl_scratch(batch, true).total) * sizeof(float);
 }
 
 int mg_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
@@ -981,27 +946,11 @@ int mg_rainbow_learn_prioritized(float* learner, const float* rows, const uint64
                                  float* rows_out, float* proj_out, float* grads_out, void* packed_out, void* scratch,
                                  size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha, double beta,
                                  double prio_eps, int64_t* idx_out, float* weight_out, void* stream) {
-  const char* what = "mg_rainbow_learn_prioritized";
-  if (int e = check_rainbow_learn(what, learner, rows, counter, capacity, batch, num_updates, hyper, noise, loss_out,
-                                  rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes))
-    return e;
-  if (int e = check_per_learn(what, tree, tree_bytes, capacity, alpha, beta, prio_eps, idx_out, weight_out, batch,
-                              scratch_bytes))
-    return e;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
-  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 0);
-  PerLearn Q = make_per_learn(L, tree, alpha, beta, prio_eps, idx_out, weight_out, scratch);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
-                             noise, loss_out, rows_out, proj_out, grads_out);
-    per_learn_set_update(Q, L, u);
-    launch_per_learn_update(Q, L, st);
-  }
-  if (packed_out)
-    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st,
-                       rainbow_learn_tensors(learner, L.eff), static_cast<uint8_t*>(packed_out));
-  return finish_launch(what);
+  RLearnCall C{learner, rows, counter, capacity, batch, num_updates, first_update, seed, first_draw, hyper, noise,
+               loss_out, rows_out, proj_out, grads_out, packed_out, scratch, scratch_bytes, true, tree, tree_bytes,
+               alpha, beta, prio_eps, idx_out, weight_out};
+  if (int e = check_rainbow_learn("mg_rainbow_learn_prioritized", C)) return e;
+  return rainbow_learn_device("mg_rainbow_learn_prioritized", C, static_cast<hipStream_t>(stream));
 }
 
 int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const uint64_t* counter, int64_t capacity,
@@ -1010,24 +959,11 @@ int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const u
                                       float* loss_out, float* rows_out, float* proj_out, float* grads_out,
                                       void* scratch, size_t scratch_bytes, void* tree, size_t tree_bytes, double alpha,
                                       double beta, double prio_eps, int64_t* idx_out, float* weight_out) {
-  const char* what = "mg_host_rainbow_learn_prioritized";
-  if (int e = check_rainbow_learn(what, learner, rows, counter, capacity, batch, num_updates, hyper, noise, loss_out,
-                                  rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes))
-    return e;
-  if (int e = check_per_learn(what, tree, tree_bytes, capacity, alpha, beta, prio_eps, idx_out, weight_out, batch,
-                              scratch_bytes))
-    return e;
-  RLearn L = make_rainbow_learn(learner, rows, counter, capacity, batch, seed, hyper, scratch);
-  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
-  PerLearn Q = make_per_learn(L, tree, alpha, beta, prio_eps, idx_out, weight_out, scratch);
-  for (int32_t u = 0; u < num_updates; ++u) {
-    rainbow_learn_set_update(L, hyper, first_update + static_cast<uint64_t>(u), first_draw + static_cast<uint64_t>(u), u,
-                             noise, loss_out, rows_out, proj_out, grads_out);
-    per_learn_set_update(Q, L, u);
-    host_per_learn_update(Q, L);
-  }
-  g_err[0] = '\0';
-  return 0;
+  RLearnCall C{learner, rows, counter, capacity, batch, num_updates, first_update, seed, first_draw, hyper, noise,
+               loss_out, rows_out, proj_out, grads_out, nullptr, scratch, scratch_bytes, true, tree, tree_bytes,
+               alpha, beta, prio_eps, idx_out, weight_out};
+  if (int e = check_rainbow_learn("mg_host_rainbow_learn_prioritized", C)) return e;
+  return rainbow_learn_host(C);
 }
 
 // ---- Rainbow noise on the device (the factors of RainbowDQN.reset_noise, :486-496, :537-541) --------

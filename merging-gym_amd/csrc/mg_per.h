@@ -1,7 +1,7 @@
 // mg_per.h -- prioritized replay for Rainbow: SumSegmentTree, MinSegmentTree and PrioritizedReplayBuffer
 // (scripts/ranbowdqn.py:130-262, :326-437) as one fp64 tree buffer beside RainbowReplay's rows, with the store,
-// sample and update kernels, the per-element functions the host twins (mg_host_per_*) run too, and the
-// launch order of the prioritized learner (mg_rainbow_learn_prioritized).
+// sample and update kernels and the per-element functions the host twins (mg_host_per_*) run too. It stands
+// alone: the learner that samples from the tree is mg_rainbow_learn.h's.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -9,7 +9,6 @@
 #include "mg_env.h"
 #include "mg_launch.h"
 #include "mg_learn_core.h"
-#include "mg_rainbow_learn.h"
 #include "mg_replay.h"
 
 namespace {
@@ -378,75 +377,6 @@ int check_per_update(const char* what, const void* tree, size_t tree_bytes, cons
   if (misaligned(counter, 7) || misaligned(idx, 7) || misaligned(priority, 3))
     return fail(hipErrorInvalidValue, "%s: counter and idx must be 8-byte, priority 4-byte aligned", what);
   return 0;
-}
-
-// ============================================================================ the prioritized learner
-// mg_rainbow_learn's scratch, then idx [B] int64 and w [B] fp32
-struct PerScratch {
-  int64_t idx, w, total;  // floats
-};
-MG_HD PerScratch per_scratch(int64_t B) {
-  PerScratch S;
-  S.idx = rl_scratch(B).total;
-  S.w = S.idx + learn_round4(2 * B);
-  S.total = S.w + learn_round4(B);
-  return S;
-}
-
-// What the two prioritized learners refuse on top of check_rainbow_learn.
-int check_per_learn(const char* what, const void* tree, size_t tree_bytes, int64_t capacity, double alpha,
-                    double beta, double prio_eps, const int64_t* idx_out, const float* weight_out,
-                    int32_t batch, size_t scratch_bytes) {
-  if (int e = check_per_tree(what, tree, tree_bytes, capacity)) return e;
-  if (int e = check_per_alpha(what, alpha)) return e;
-  if (int e = check_per_beta(what, beta)) return e;
-  if (!(prio_eps >= 0.0)) return fail(hipErrorInvalidValue, "%s: need prio_eps >= 0", what);
-  if (misaligned(idx_out, 7) || misaligned(weight_out, 3))
-    return fail(hipErrorInvalidValue, "%s: idx_out must be 8-byte, weight_out 4-byte aligned", what);
-  if (scratch_bytes < static_cast<size_t>(per_scratch(batch).total) * sizeof(float))
-    return fail(hipErrorInvalidValue, "%s: scratch smaller than mg_rainbow_learn_prioritized_scratch_bytes(batch)", what);
-  return 0;
-}
-
-// The fields of one call: the sample of update u (after rainbow_learn_set_update) and the update behind it.
-struct PerLearn {
-  PerSample P;
-  PerUpdate U;
-  int64_t* idx_out;
-  float* weight_out;
-};
-PerLearn make_per_learn(RLearn& L, void* tree, double alpha, double beta, double prio_eps, int64_t* idx_out,
-                        float* weight_out, void* scratch) {
-  const PerScratch S = per_scratch(L.B);
-  float* s = static_cast<float*>(scratch);
-  PerLearn Q{};
-  Q.P.T = Q.U.T = per_tree(tree, L.cap);
-  Q.P.counter = Q.U.counter = L.counter;
-  Q.P.beta = beta, Q.P.seed = L.seed, Q.P.B = Q.U.B = L.B;
-  Q.P.idx = reinterpret_cast<int64_t*>(s + S.idx), Q.P.w = s + S.w;
-  Q.U.alpha = alpha, Q.U.idx = Q.P.idx, Q.U.priority = L.lossb;
-  Q.U.add = static_cast<float>(prio_eps), Q.U.has_add = 1;
-  Q.idx_out = idx_out, Q.weight_out = weight_out;
-  L.pidx = Q.P.idx, L.pw = Q.P.w;
-  return Q;
-}
-void per_learn_set_update(PerLearn& Q, const RLearn& L, int32_t u) {
-  Q.P.draw = L.draw;
-  Q.P.idx_out = Q.idx_out ? Q.idx_out + static_cast<int64_t>(u) * L.B : nullptr;
-  Q.P.w_out = Q.weight_out ? Q.weight_out + static_cast<int64_t>(u) * L.B : nullptr;
-}
-
-// One prioritized update on the device: the sample, mg_rainbow_learn's seven launches reading its rows and
-// weights, the priorities loss_b + prio_eps back into the tree. host_per_learn_update restates it.
-void launch_per_learn_update(const PerLearn& Q, const RLearn& L, hipStream_t st) {
-  hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(L.B)), dim3(kBlock), 0, st, Q.P);
-  launch_rainbow_learn_update(L, st);
-  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(kPerTail), 0, st, Q.U);
-}
-void host_per_learn_update(const PerLearn& Q, const RLearn& L) {
-  for (int b = 0; b < L.B; ++b) per_sample_at(Q.P, b);
-  host_rainbow_learn_update(L);
-  host_per_update(Q.U);
 }
 
 }  // namespace

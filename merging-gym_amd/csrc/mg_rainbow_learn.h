@@ -1,6 +1,8 @@
 // mg_rainbow_learn.h -- Rainbow's compute_td_loss on the device: the done-carrying replay store, the C51
 // projection, the noisy-net forward and backward, Adam and the noise reset, with the per-element functions
-// the host twin (mg_host_rainbow_learn) runs too.
+// the host twins (mg_host_rainbow_learn*) run too. The learner in both forms: the plain one is the prioritized
+// one (mg_per.h's tree, sample and update) without a tree, so a call has one check, one launch order beside
+// its host twin and one pair of drivers; the replay stores likewise.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -8,6 +10,7 @@
 #include "mg_env.h"
 #include "mg_launch.h"
 #include "mg_learn_core.h"
+#include "mg_per.h"
 #include "mg_rainbow.h"
 #include "mg_replay.h"
 
@@ -84,10 +87,10 @@ MG_HD RlNoisy rl_noisy(int l) {
 MG_HD int rl_layer_of_eps(int e) { return e < 4160 ? 0 : e < 7475 ? 1 : e < 11635 ? 2 : 3; }
 MG_HD int rl_layer_of_param(int i) { return i < kRlPlain + 8320 ? 0 : i < kRlPlain + 14950 ? 1 : i < kRlPlain + 23270 ? 2 : 3; }
 
-struct RlScratch {  // sections (floats), each a multiple of four
-  int64_t rows, h1, h2, hv, ha, dlog, dhv, dha, dh2, dh1, lossb, g, geff, eff, total;
+struct RlScratch {  // sections (floats), each a multiple of four; prioritized: then idx [B] int64 and w [B]
+  int64_t rows, h1, h2, hv, ha, dlog, dhv, dha, dh2, dh1, lossb, g, geff, eff, pidx, pw, total;
 };
-MG_HD RlScratch rl_scratch(int64_t B) {
+MG_HD RlScratch rl_scratch(int64_t B, bool prioritized) {
   RlScratch S;
   S.rows = 0;
   S.h1 = S.rows + B * kRlRow;
@@ -103,7 +106,9 @@ MG_HD RlScratch rl_scratch(int64_t B) {
   S.g = S.lossb + learn_round4(B);
   S.geff = S.g + kRlPlain;
   S.eff = S.geff + learn_round4(kRlEps);
-  S.total = S.eff + learn_round4(2 * kRlEps);
+  S.pidx = S.eff + learn_round4(2 * kRlEps);
+  S.pw = S.pidx + (prioritized ? learn_round4(2 * B) : 0);
+  S.total = S.pw + (prioritized ? learn_round4(B) : 0);
   return S;
 }
 
@@ -503,58 +508,123 @@ int check_rainbow_store(const char* what, const float* rows, const uint64_t* cou
   return 0;
 }
 
-// What mg_rainbow_learn and mg_host_rainbow_learn refuse, before anything is read or launched.
-int check_rainbow_learn(const char* what, const float* learner, const float* rows, const uint64_t* counter,
-                        int64_t capacity, int32_t batch, int32_t num_updates, const mg_dqn_hyper* hyper,
-                        const float* noise, const float* loss_out, const float* rows_out, const float* proj_out,
-                        const float* grads_out, const void* packed_out, const void* scratch, size_t scratch_bytes) {
-  if (!learner || !rows || !counter || !hyper || !scratch) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
-  if (int e = check_learn_sizes(what, batch, capacity, num_updates)) return e;
-  if (num_updates > 0 && !noise)
+// A store after its checks, on the stream or (host) as loops: the rows, the tree's part if there is a tree, then
+// the counter moves.
+void rainbow_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
+                   int32_t num_steps, void* tree, double alpha, bool host, hipStream_t st) {
+  RlStore R{};
+  R.X = *tr;
+  R.n = n;
+  R.total = n * num_steps;
+  if (host) {
+    for (int64_t i = 0; i < R.total; ++i) rl_store_at(R, counter, rows, capacity, i);
+    if (tree) host_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha);
+    *counter += static_cast<uint64_t>(R.total);
+    return;
+  }
+  hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
+  if (tree) launch_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha, st);
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+}
+
+// One call of mg_rainbow_learn, mg_rainbow_learn_prioritized or a host twin: the arguments as the entry point
+// took them (packed_out NULL on the host; without `prioritized` the fields behind it stay zero), then what
+// make_rainbow_learn derives from them.
+struct RLearnCall {
+  float* learner;
+  const float* rows;
+  const uint64_t* counter;
+  int64_t capacity;
+  int32_t batch, num_updates;
+  uint64_t first_update, seed, first_draw;
+  const mg_dqn_hyper* hyper;
+  const float* noise;
+  float *loss_out, *rows_out, *proj_out, *grads_out;
+  void *packed_out, *scratch;
+  size_t scratch_bytes;
+  bool prioritized;
+  void* tree;
+  size_t tree_bytes;
+  double alpha, beta, prio_eps;
+  int64_t* idx_out;
+  float* weight_out;
+  RLearn L;
+  PerSample P;  // with `prioritized`: the sample in front of the seven launches
+  PerUpdate U;  // and the priorities behind them
+};
+
+// What the four learners refuse, before anything is read or launched.
+int check_rainbow_learn(const char* what, const RLearnCall& C) {
+  if (!C.learner || !C.rows || !C.counter || !C.hyper || !C.scratch)
+    return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (int e = check_learn_sizes(what, C.batch, C.capacity, C.num_updates)) return e;
+  if (C.num_updates > 0 && !C.noise)
     return fail(hipErrorInvalidValue, "%s: noise is NULL (num_updates x 2 x 1124 factors)", what);
-  if (int e = check_adam_betas(what, hyper)) return e;
-  if (misaligned(learner, 15) || misaligned(scratch, 15) || misaligned(packed_out, 15) || misaligned(rows, 7) ||
-      misaligned(counter, 7) || misaligned(noise, 3) || misaligned(loss_out, 3) || misaligned(rows_out, 3) ||
-      misaligned(proj_out, 3) || misaligned(grads_out, 3))
+  if (int e = check_adam_betas(what, C.hyper)) return e;
+  if (misaligned(C.learner, 15) || misaligned(C.scratch, 15) || misaligned(C.packed_out, 15) ||
+      misaligned(C.rows, 7) || misaligned(C.counter, 7) || misaligned(C.noise, 3) || misaligned(C.loss_out, 3) ||
+      misaligned(C.rows_out, 3) || misaligned(C.proj_out, 3) || misaligned(C.grads_out, 3))
     return fail(hipErrorInvalidValue,
                 "%s: learner, scratch and packed_out must be 16-byte, rows and counter 8-byte, noise and the "
                 "optional outputs 4-byte aligned", what);
-  if (scratch_bytes < static_cast<size_t>(rl_scratch(batch).total) * sizeof(float))
+  if (C.scratch_bytes < static_cast<size_t>(rl_scratch(C.batch, false).total) * sizeof(float))
     return fail(hipErrorInvalidValue, "%s: scratch smaller than mg_rainbow_learn_scratch_bytes(batch)", what);
+  if (!C.prioritized) return 0;
+  if (int e = check_per_tree(what, C.tree, C.tree_bytes, C.capacity)) return e;
+  if (int e = check_per_alpha(what, C.alpha)) return e;
+  if (int e = check_per_beta(what, C.beta)) return e;
+  if (!(C.prio_eps >= 0.0)) return fail(hipErrorInvalidValue, "%s: need prio_eps >= 0", what);
+  if (misaligned(C.idx_out, 7) || misaligned(C.weight_out, 3))
+    return fail(hipErrorInvalidValue, "%s: idx_out must be 8-byte, weight_out 4-byte aligned", what);
+  if (C.scratch_bytes < static_cast<size_t>(rl_scratch(C.batch, true).total) * sizeof(float))
+    return fail(hipErrorInvalidValue, "%s: scratch smaller than mg_rainbow_learn_prioritized_scratch_bytes(batch)", what);
   return 0;
 }
 
-// The fields of RLearn that do not change from one update of a call to the next.
-RLearn make_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,
-                          uint64_t seed, const mg_dqn_hyper* hyper, void* scratch) {
-  const RlScratch S = rl_scratch(batch);
-  float* s = static_cast<float*>(scratch);
-  RLearn L{};
-  L.buf = learner;
-  L.ring = rows, L.counter = counter, L.cap = capacity, L.seed = seed, L.B = batch;
+// The fields of L, P and U that do not change from one update of a call to the next.
+void make_rainbow_learn(RLearnCall& C) {
+  const RlScratch S = rl_scratch(C.batch, C.prioritized);
+  float* s = static_cast<float*>(C.scratch);
+  RLearn& L = C.L;
+  L.buf = C.learner;
+  L.ring = C.rows, L.counter = C.counter, L.cap = C.capacity, L.seed = C.seed, L.B = C.batch;
   L.rows = s + S.rows, L.h1 = s + S.h1, L.h2 = s + S.h2, L.hv = s + S.hv, L.ha = s + S.ha, L.dlog = s + S.dlog;
   L.dhv = s + S.dhv, L.dha = s + S.dha, L.dh2 = s + S.dh2, L.dh1 = s + S.dh1, L.lossb = s + S.lossb;
   L.g = s + S.g, L.geff = s + S.geff, L.eff = s + S.eff;
-  L.gamma = static_cast<float>(hyper->gamma);
-  L.inv_b = static_cast<float>(1.0 / batch);
-  return L;
+  L.gamma = static_cast<float>(C.hyper->gamma);
+  L.inv_b = static_cast<float>(1.0 / C.batch);
+  if (!C.prioritized) return;
+  C.P.T = C.U.T = per_tree(C.tree, C.capacity);
+  C.P.counter = C.U.counter = C.counter;
+  C.P.beta = C.beta, C.P.seed = C.seed, C.P.B = C.U.B = C.batch;
+  C.P.idx = reinterpret_cast<int64_t*>(s + S.pidx), C.P.w = s + S.pw;
+  C.U.alpha = C.alpha, C.U.idx = C.P.idx, C.U.priority = L.lossb;
+  C.U.add = static_cast<float>(C.prio_eps), C.U.has_add = 1;
+  L.pidx = C.P.idx, L.pw = C.P.w;
 }
 
 // Update number u of a call: its draw, factors, optional outputs and Adam's step t + 1 (t = first_update + u).
-void rainbow_learn_set_update(RLearn& L, const mg_dqn_hyper* h, uint64_t t, uint64_t draw, int32_t u, const float* noise,
-                              float* loss_out, float* rows_out, float* proj_out, float* grads_out) {
-  L.A = learn_adam_scalars(h, t);
-  L.draw = draw;
-  L.noise = noise + static_cast<int64_t>(u) * 2 * kRlFactors;
-  L.loss_out = loss_out ? loss_out + u : nullptr;
-  L.rows_out = rows_out ? rows_out + static_cast<int64_t>(u) * L.B * kRlRow : nullptr;
-  L.proj_out = proj_out ? proj_out + static_cast<int64_t>(u) * L.B * kRbAtoms : nullptr;
-  L.grads_out = grads_out ? grads_out + static_cast<int64_t>(u) * kRlParams : nullptr;
+void rainbow_learn_set_update(RLearnCall& C, int32_t u) {
+  RLearn& L = C.L;
+  const int64_t ub = static_cast<int64_t>(u) * L.B;
+  L.A = learn_adam_scalars(C.hyper, C.first_update + static_cast<uint64_t>(u));
+  L.draw = C.P.draw = C.first_draw + static_cast<uint64_t>(u);
+  L.noise = C.noise + static_cast<int64_t>(u) * 2 * kRlFactors;
+  L.loss_out = C.loss_out ? C.loss_out + u : nullptr;
+  L.rows_out = C.rows_out ? C.rows_out + ub * kRlRow : nullptr;
+  L.proj_out = C.proj_out ? C.proj_out + ub * kRbAtoms : nullptr;
+  L.grads_out = C.grads_out ? C.grads_out + static_cast<int64_t>(u) * kRlParams : nullptr;
+  C.P.idx_out = C.idx_out ? C.idx_out + ub : nullptr;
+  C.P.w_out = C.weight_out ? C.weight_out + ub : nullptr;
 }
 
-// One update on the device (mg_rainbow_learn), after rainbow_learn_set_update: the launch order that
-// host_rainbow_learn_update below restates loop for loop (the last launch leaves the next update's weights).
-void launch_rainbow_learn_update(const RLearn& L, hipStream_t st) {
+// One update on the device, after rainbow_learn_set_update: the launch order that host_rainbow_learn_update
+// below restates loop for loop. With a tree the sample goes in front and its rows and weights are what the
+// seven launches read; the priorities loss_b + prio_eps go back into the tree behind them. The last of the
+// seven leaves the next update's effective weights.
+void launch_rainbow_learn_update(const RLearnCall& C, hipStream_t st) {
+  const RLearn& L = C.L;
+  if (C.prioritized) hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(L.B)), dim3(kBlock), 0, st, C.P);
   hipLaunchKernelGGL(rl_forward_kernel, dim3(L.B), dim3(2 * kRlThreads), 0, st, L);
   const LearnBwd G0 = rl_bwd_layer(L, 0), G1 = rl_bwd_layer(L, 1), G2 = rl_bwd_layer(L, 2), G3 = rl_bwd_layer(L, 3);
   hipLaunchKernelGGL(rl_bwd_heads_kernel, dim3(grid_blocks(learn_bwd_items(G0) + learn_bwd_items(G1))), dim3(kBlock),
@@ -567,18 +637,14 @@ void launch_rainbow_learn_update(const RLearn& L, hipStream_t st) {
   }
   hipLaunchKernelGGL(rl_adam_kernel, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
   hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 1);
+  if (C.prioritized) hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(kPerTail), 0, st, C.U);
 }
 
-// What rainbow_pack_kernel packs for acting: the current model's plain layers, effective weights e = L.eff, support.
-RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
-  const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
-  return RbTensors{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
-                   e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
-                   e + A1.e, e + A1.e + A1.out * kRbHS, e + A2.e, e + A2.e + A2.out * kRbHS, learner + kRlOffZ};
-}
-
-// One update on the host (mg_host_rainbow_learn): the kernels' per-item functions in the kernels' order.
-void host_rainbow_learn_update(const RLearn& L) {
+// One update on the host: the kernels' per-item functions in the kernels' order.
+void host_rainbow_learn_update(const RLearnCall& C) {
+  const RLearn& L = C.L;
+  if (C.prioritized)
+    for (int b = 0; b < L.B; ++b) per_sample_at(C.P, b);
   const uint64_t live = learn_rows_live(L.cap, L.counter, 1);
   for (int b = 0; b < L.B; ++b) host_rl_forward_row(L, live, b);
   for (int which = 0; which < 6; ++which) {
@@ -589,6 +655,45 @@ void host_rainbow_learn_update(const RLearn& L) {
   }
   for (int i = 0; i <= kRlParams; ++i) rl_adam_at(L, i);
   for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, true);
+  if (C.prioritized) host_per_update(C.U);
+}
+
+// What rainbow_pack_kernel packs for acting: the current model's plain layers, effective weights e = L.eff, support.
+RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
+  const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
+  return RbTensors{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
+                   e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
+                   e + A1.e, e + A1.e + A1.out * kRbHS, e + A2.e, e + A2.e + A2.out * kRbHS, learner + kRlOffZ};
+}
+
+// ---------------------------------------------------------------------------- the drivers of a call
+// The device learners after their check: the effective weights of the stored noise (every update's last of the
+// seven launches leaves the next one's), the updates back to back on the stream, then the acting kernels' layout
+// of the current model's effective weights.
+int rainbow_learn_device(const char* what, RLearnCall& C, hipStream_t st) {
+  make_rainbow_learn(C);
+  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, C.L, 0);
+  for (int32_t u = 0; u < C.num_updates; ++u) {
+    rainbow_learn_set_update(C, u);
+    launch_rainbow_learn_update(C, st);
+  }
+  if (C.packed_out)
+    hipLaunchKernelGGL(rainbow_pack_kernel, dim3(grid_blocks(kRbNetBytes / 4)), dim3(kBlock), 0, st,
+                       rainbow_learn_tensors(C.learner, C.L.eff), static_cast<uint8_t*>(C.packed_out));
+  return finish_launch(what);
+}
+
+// The host learners after their check.
+int rainbow_learn_host(RLearnCall& C) {
+  make_rainbow_learn(C);
+  for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(C.L, i, false);
+  for (int32_t u = 0; u < C.num_updates; ++u) {
+    rainbow_learn_set_update(C, u);
+    host_rainbow_learn_update(C);
+  }
+  g_err[0] = '\0';
+  return 0;
 }
 
 }  // namespace
+

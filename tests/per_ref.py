@@ -54,10 +54,57 @@ def expected_row(k):
     return row
 
 
+STORE_CAP, STORE_FIRST = 13, 3
+
+
+def store_case(use_flags):
+    """n = 5 envs x T = 4 steps for a ring of STORE_CAP that holds STORE_FIRST rows: 20 transitions, so the oldest
+    are skipped, the ring wraps and every slot is written. Two steps in three are done (s' from final_obs), the
+    others take s' from obs. With use_flags the action and done travel as a rollout's [T, N, 4] bytes in place of
+    a1 / done."""
+    tr = transitions(5, 4, first=STORE_FIRST)
+    k = STORE_FIRST + np.arange(20).reshape(4, 5)
+    tr["done"] = (k % 3 != 0).astype(np.uint8)
+    if use_flags:
+        flags = np.zeros((4, 5, 4), np.uint8)
+        flags[..., 0], flags[..., 1], flags[..., 2] = tr["a1"].view(np.uint8), 9, tr["done"]
+        tr = dict(tr, flags=flags, a1=None, done=None)
+    return tr
+
+
+def pushed(ring, counter, tr):
+    """Sequential replay_buffer.push calls of tr (with a1 and done) in (step, env) order on a copy of a numpy
+    ring: (ring, counter)."""
+    ring = ring.copy()
+    T, n = tr["a1"].shape
+    for t in range(T):
+        for i in range(n):
+            row = np.zeros(ROW, np.float32)
+            row[:10] = tr["obs_first"][i] if t == 0 else tr["obs"][t - 1, i]
+            row[10], row[11], row[22] = tr["a1"][t, i], tr["rew"][t, i, 0], tr["done"][t, i]
+            row[12:22] = tr["final_obs"][t, i] if tr["done"][t, i] else tr["obs"][t, i]
+            ring[counter % len(ring)] = row
+            counter += 1
+    return ring, counter
+
+
+def learn_case(size, alpha):
+    """A wrapped HostPer with recorded observations as rows and a tree 10 rounds of updates have shaped."""
+    import rainbow_learn_ref as R
+
+    h = HostPer(size, alpha)
+    h.push_many(size + size // 2 + 1, n=min(size, 500))
+    h.rows[:] = R.replay_rows(size)
+    for r in range(10):
+        idx, _ = h.sample(BATCH, BETA, 1, r)
+        h.update(idx, np.exp(np.random.default_rng(r).uniform(np.log(1e-3), np.log(8.0), BATCH)).astype(np.float32))
+    return h
+
+
 def transitions_struct(nat, tr, pointer=lambda a: a.ctypes.data):
     p = lambda name: None if tr.get(name) is None else pointer(tr[name])  # noqa: E731
     return nat.Transitions(p("obs_first"), p("obs"), p("final_obs"), p("a1"), p("rew"), p("done"), None, None, None,
-                           None, None, None)
+                           None, p("flags"), None)
 
 
 class HostPer:
@@ -94,7 +141,7 @@ class HostPer:
         return other
 
     def store(self, tr):
-        T, n = tr["a1"].shape
+        T, n = tr["rew"].shape[:2]
         X = transitions_struct(self.nat, tr)
         self.check(self.lib.mg_host_per_store(self.rows.ctypes.data, self.counter.ctypes.data, self.capacity,
                                               ctypes.byref(X), n, T, self.tree.ctypes.data, self.nbytes, self.alpha),

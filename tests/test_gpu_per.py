@@ -28,8 +28,9 @@ def _device(torch, size, alpha):
 
 
 def _store(torch, rp, tr):
-    dev = lambda x: torch.from_numpy(x).to(DEV)  # noqa: E731
-    rp.store(dev(tr["obs_first"]), dev(tr["obs"]), dev(tr["a1"]), dev(tr["rew"]), dev(tr["done"]), dev(tr["final_obs"]))
+    dev = lambda x: None if x is None else torch.from_numpy(x).to(DEV)  # noqa: E731
+    rp.store(dev(tr["obs_first"]), dev(tr["obs"]), dev(tr["a1"]), dev(tr["rew"]), dev(tr["done"]), dev(tr["final_obs"]),
+             dev(tr.get("flags")))
 
 
 def _assert_same_state(rp, h, what=""):
@@ -108,32 +109,73 @@ def test_alpha_one_fixture_rounds_on_the_device(torch, size):
         assert P.ulp32_distance(w.cpu().numpy(), g[key + "/w"][r].astype(np.float32)).max() <= 1, r
 
 
-def _learn_case(size, alpha):
-    """A wrapped HostPer with recorded observations as rows and a tree 10 rounds of updates have shaped."""
-    h = P.HostPer(size, alpha)
-    h.push_many(size + size // 2 + 1, n=min(size, 500))
-    h.rows[:] = R.replay_rows(size)
-    for r in range(10):
-        idx, _ = h.sample(P.BATCH, P.BETA, 1, r)
-        h.update(idx, np.exp(np.random.default_rng(r).uniform(np.log(1e-3), np.log(8.0), P.BATCH)).astype(np.float32))
-    return h
+@pytest.mark.parametrize("use_flags", (False, True), ids=("a1-done", "flags"))
+def test_the_stores_leave_the_same_rows_and_counter(torch, use_flags):
+    """P.store_case through RainbowReplay.store, PrioritizedRainbowReplay.store and mg_host_per_store: one store
+    helper behind all three, so the rows and the counter are the same bits, and those of sequential pushes."""
+    from merging_gym import RainbowReplay
+
+    first, tr = P.transitions(P.STORE_FIRST, 1), P.store_case(use_flags)
+    plain, per, h = RainbowReplay(P.STORE_CAP, device=DEV), _device(torch, P.STORE_CAP, 0.6), P.HostPer(P.STORE_CAP, 0.6)
+    for rp in (plain, per):
+        _store(torch, rp, first)
+        _store(torch, rp, tr)
+    h.store(first)
+    h.store(tr)
+    want, counter = P.pushed(*P.pushed(np.zeros((P.STORE_CAP, P.ROW), np.float32), 0, first), P.store_case(False))
+    assert counter == P.STORE_FIRST + 20 == int(h.counter[0]) and np.array_equal(bits(h.rows), bits(want))
+    for rp in (plain, per):
+        assert int(rp._counter.item()) == counter, type(rp).__name__
+        assert np.array_equal(bits(rp.memory.cpu().numpy()), bits(want)), type(rp).__name__
+    _assert_same_state(per, h, "the tree")
+
+
+def _prioritized(torch, h, B, eps=1e-5):
+    """A PrioritizedRainbowLearner (the soft golden state, seed 3, noise generator 11, beta 0.4) on a device copy of
+    the HostPer h."""
+    from merging_gym import PrioritizedRainbowLearner
+
+    rp = _device(torch, h.capacity, h.alpha)
+    rp.memory.copy_(torch.from_numpy(h.rows))
+    rp._counter.fill_(int(h.counter[0]))
+    rp._tree.copy_(torch.from_numpy(h.tree))
+    return PrioritizedRainbowLearner(R.golden_state(1, "soft"), rp, batch_size=B, seed=3,
+                                     generator=torch.Generator().manual_seed(11), device=DEV, beta=0.4, prio_eps=eps)
+
+
+def _learn_all(lr, U, beta):
+    return lr.learn(U, return_loss=True, return_rows=True, return_proj=True, return_grads=True, return_idx=True,
+                    return_weights=True, beta=beta)
+
+
+def test_three_updates_in_one_call_equal_three_calls_of_one(torch):
+    """U = 3, B = 32 on the wrapped ring of 13 (a 16-leaf tree), alpha 0.6, beta 0.5: learn(3) against learn(1)
+    three times with equal noise generators, bit for bit -- the learner buffer, the acting net, every tree node and
+    max_priority, the rows and the counter, and all six outputs concatenated."""
+    h = P.learn_case(13, 0.6)
+    whole, single = _prioritized(torch, h, 32), _prioritized(torch, h, 32)
+    a = _learn_all(whole, 3, 0.5)
+    b = [torch.cat(parts) for parts in zip(*(_learn_all(single, 1, 0.5) for _ in range(3)))]
+    raw = lambda t: t.contiguous().view(torch.uint8)  # noqa: E731
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert x.shape == y.shape and torch.equal(raw(x), raw(y)), k
+    assert torch.equal(raw(whole._buf), raw(single._buf)) and torch.equal(whole.net.packed, single.net.packed)
+    for name in ("_tree", "memory", "_counter"):
+        assert torch.equal(raw(getattr(whole.replay, name)), raw(getattr(single.replay, name))), name
+    assert (whole.learn_step_counter, single.draw_counter) == (3, 3)
+    assert not np.array_equal(P.f64bits(whole.replay._tree.cpu().numpy()), P.f64bits(h.tree))  # priorities moved
+    assert len(np.unique(a[4].cpu().numpy())) > 4  # a real sample
 
 
 @pytest.mark.parametrize("size,alpha", ((13, 1.0), (13, 0.6), (3000, 1.0), (3000, 0.6)))
 def test_prioritized_learner_equals_its_host_twin(torch, size, alpha):
-    from merging_gym import PrioritizedRainbowLearner, RainbowNet
+    from merging_gym import RainbowNet
 
     B, U, beta, eps = 32, 3, 0.5, 1e-5
-    h = _learn_case(size, alpha)
-    rp = _device(torch, size, alpha)
-    rp.memory.copy_(torch.from_numpy(h.rows))
-    rp._counter.fill_(int(h.counter[0]))
-    rp._tree.copy_(torch.from_numpy(h.tree))
-    sd = R.golden_state(1, "soft")
-    lr = PrioritizedRainbowLearner(sd, rp, batch_size=B, seed=3, generator=torch.Generator().manual_seed(11), device=DEV,
-                                   beta=0.4, prio_eps=eps)
-    got = [t.cpu().numpy() for t in lr.learn(U, return_loss=True, return_rows=True, return_proj=True, return_grads=True,
-                                             return_idx=True, return_weights=True, beta=beta)]
+    h = P.learn_case(size, alpha)
+    lr = _prioritized(torch, h, B, eps)
+    rp, sd = lr.replay, R.golden_state(1, "soft")
+    got = [t.cpu().numpy() for t in _learn_all(lr, U, beta)]
     want = P.run_host_prioritized(R.learner_numpy(sd), h, B, U, beta, eps, seed=3, noise_f=R.noise(U))
     R.assert_same((lr._buf.cpu().numpy(), got[:4]), (want[0], list(want[1:5])))
     assert np.array_equal(got[4], want[5]) and np.array_equal(bits(got[5]), bits(want[6]))

@@ -152,6 +152,22 @@ def test_store_larger_than_the_ring_keeps_the_newest_and_rebuilds_every_node():
                for i in range(1, h.C))
 
 
+@pytest.mark.parametrize("use_flags", (False, True), ids=("a1-done", "flags"))
+def test_host_store_equals_sequential_pushes(use_flags):
+    """P.store_case (the device stores' test runs it too): 20 transitions into the ring of 13 from position 3,
+    the action and done from a1 / done or from a rollout's flags."""
+    h = P.HostPer(P.STORE_CAP, 0.6)
+    first = P.transitions(P.STORE_FIRST, 1)
+    h.store(first)
+    h.store(P.store_case(use_flags))
+    want, counter = P.pushed(*P.pushed(np.zeros((P.STORE_CAP, P.ROW), np.float32), 0, first), P.store_case(False))
+    assert int(h.counter[0]) == counter == P.STORE_FIRST + 20
+    assert np.array_equal(h.rows.view(np.uint32), want.view(np.uint32))
+    assert set(want[:, 22].tolist()) == {0.0, 1.0}  # both sources of s'
+    v = h.sum[h.C]  # max_priority ** alpha of the fresh tree, in every written leaf
+    assert v == 1.0 and (h.sum[h.C:h.C + P.STORE_CAP] == v).all() and (h.min[h.C:h.C + P.STORE_CAP] == v).all()
+
+
 def test_tree_round_trip_continues_bit_for_bit():
     """What PrioritizedRainbowReplay.state_dict carries: the rows, the counter and the tree buffer."""
     runs = []

@@ -36,6 +36,31 @@ def _case(size=13, alpha=0.6):
     return h
 
 
+def test_three_updates_in_one_call_equal_three_calls_of_one():
+    """U = 3, B = 32 on the wrapped ring of 13 (a 16-leaf tree), alpha 0.6, beta 0.5, from the device test's
+    starting point: call u of the three runs with first_update = first_draw = u and noise slice u. Bit for bit:
+    the learner buffer, every tree node and max_priority, the rows and the counter, and all six outputs
+    concatenated."""
+    B, U = 32, 3
+    L0 = R.learner_numpy(R.golden_state(1, "soft"))
+    nf = R.noise(U)
+    start = P.learn_case(13, 0.6)
+    single, whole = start.clone(), start.clone()
+    L, seq = L0, []
+    for u in range(U):
+        seq.append(P.run_host_prioritized(L, single, B, 1, BETA, EPS, first_update=u, seed=SEED, first_draw=u,
+                                          noise_f=nf[u:u + 1]))
+        L = seq[-1][0]
+    all3 = P.run_host_prioritized(L0, whole, B, U, BETA, EPS, seed=SEED, noise_f=nf)
+    assert np.array_equal(bits(all3[0]), bits(L))
+    assert np.array_equal(P.f64bits(whole.tree), P.f64bits(single.tree))
+    assert np.array_equal(bits(whole.rows), bits(single.rows)) and whole.counter[0] == single.counter[0]
+    for k in range(1, 7):
+        assert np.array_equal(all3[k].view(np.uint8), np.concatenate([s[k] for s in seq]).view(np.uint8)), k
+    assert not np.array_equal(P.f64bits(whole.tree), P.f64bits(start.tree))  # the priorities moved
+    assert len(np.unique(all3[5])) > 4 and len(np.unique(all3[6])) > 1  # a real sample with real weights
+
+
 def test_weighted_order_restated_in_python():
     """Three updates, one call each. Per update: idx and w are the sample of the tree as it stands; loss_out is
     the chain over fp32(w_b * loss_b) times fp32(1 / B); the priorities written back are fp32(loss_b + fp32(eps))
