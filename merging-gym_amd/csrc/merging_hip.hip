@@ -23,7 +23,7 @@
 //
 // One translation unit in parts, one subsystem each. Every part includes what it uses and compiles
 // on its own; this file includes them in the order that fixes the kernels' order in the code object,
-// and keeps only the C entry points (include/merging_hip.h).
+// and keeps only the C entry points (include/merging_hip.h): a call's checks, fill and launches are in its part.
 #pragma clang fp contract(off)
 
 #include "mg_common.h"          // block size, MG_HD, vector types, st_out / st_state
@@ -33,11 +33,11 @@
 #include "mg_step.h"            // step_kernel, rollout_kernel
 #include "mg_qnet.h"            // the bf16 MFMA Q-net: pack kernels, forwards
 #include "mg_rainbow.h"         // Rainbow's acting net: pack kernel, MFMA forward, the fp32 head
-#include "mg_rollout_qnet.h"    // config 5: qnet_rollout_ws_kernel
+#include "mg_rollout_qnet.h"    // config 5: qnet_rollout_ws_kernel, lone and with the member in the grid, their host side
 #include "mg_rollout_hdqn.h"    // the h-DQN acting loop: hdqn_rollout_kernel
 #include "mg_rollout_rainbow.h" // Rainbow's acting loop: rainbow_rollout_kernel
 #include "mg_reset_observe.h"   // reset_kernel, observe_kernel
-#include "mg_replay.h"          // the replay ring: scan, write and sample kernels, counter_add_kernel
+#include "mg_replay.h"          // the replay ring: scan, write and sample kernels, counter_add_kernel, the stores' host side
 #include "mg_launch.h"          // error text, armed events, argument checks, launch helpers
 #include "mg_mpc_qp.h"          // mpc_qp_constants (host only)
 #include "mg_stats_reduce.h"    // the fixed-order statistics reduction, goal_status_kernel
@@ -207,31 +207,17 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
                     uint64_t opp_greedy_threshold, const void* opp_net, uint32_t flags, void* stream) {
   if (int e = check_rollout_args(params, state, traj, n)) return e;
   if (int e = check_packed_net(net, "net must be a 16-byte aligned packed Q-net")) return e;
-  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
-    return fail(hipErrorInvalidValue, "%s", "need num_steps >= 0 and 1 <= out_dim <= 8");
-  if (opponent_mode < 0 || opponent_mode > 3)
-    return fail(hipErrorInvalidValue, "%s",
-                "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (opp_net)");
+  if (int e = check_qrollout_dims_mode(false, num_steps, out_dim, opponent_mode)) return e;
   if (opponent_mode == 3)
     if (int e = check_packed_net(opp_net, "opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net")) return e;
   if (int e = check_traj(traj)) return e;
   if (n == 0 || num_steps == 0) return 0;
   QRollout R = make_rollout<QRollout>(params, state, traj, stats, seed, first_step, env_offset, n, num_steps, flags);
-  R.net = static_cast<const uint8_t*>(net);
-  R.opp_net = static_cast<const uint8_t*>(opp_net);
-  R.greedy_thr = greedy_threshold;
-  R.opp_greedy_thr = opp_greedy_threshold;
-  R.out_dim = out_dim;
-  R.fin = finish_bound(*params);
-  const bool checked = out_dim > MG_NUM_ACTIONS;  // argmax may name an action past action_dict
-  // a net opponent's instances are always checked (the instances come out in the code object in the
-  // order they are first named here)
-  void (*const kernel)(QRollout) =
-      opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true> : qnet_rollout_ws_kernel<0, false>)
-      : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true> : qnet_rollout_ws_kernel<1, false>)
-      : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true>
-                           : qnet_rollout_ws_kernel<3, true>;
-  launch(kernel, grid_blocks(n, kQWsEnvs), kQWsThreads, static_cast<hipStream_t>(stream), R);
+  R.out_dim = out_dim, R.fin = finish_bound(*params);
+  R.net = static_cast<const uint8_t*>(net), R.opp_net = static_cast<const uint8_t*>(opp_net);
+  R.greedy_thr = greedy_threshold, R.opp_greedy_thr = opp_greedy_threshold;
+  launch(qnet_rollout_instance<false>(opponent_mode, out_dim > MG_NUM_ACTIONS), grid_blocks(n, kQWsEnvs), kQWsThreads,
+         static_cast<hipStream_t>(stream), R);
   return finish_launch("mg_rollout_qnet");
 }
 
@@ -240,7 +226,7 @@ int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const m
                          uint64_t first_step, int32_t num_steps, const mg_qnet_actor* actors, int32_t out_dim,
                          int32_t opponent_mode, uint32_t flags, void* stream) {
   const char* const who = "mg_rollout_qnet_many: %s";
-  if (members < 1 || members > kQMaxMembers) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
+  if (!members_ok(members)) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
   if (n_member < 0) return fail(hipErrorInvalidValue, who, "n_member < 0");
   if (n_member % 64 != 0)
     return fail(hipErrorInvalidValue, who,
@@ -251,42 +237,15 @@ int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const m
   const int64_t n = n_member * members;
   if (int e = check_rollout_args(params, state, traj, n)) return e;
   if (!actors) return fail(hipErrorInvalidValue, who, "actors is NULL (members mg_qnet_actor entries)");
-  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
-    return fail(hipErrorInvalidValue, who, "need num_steps >= 0 and 1 <= out_dim <= 8");
-  if (opponent_mode < 0 || opponent_mode > 3)
-    return fail(hipErrorInvalidValue, who,
-                "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (each member's opp_net)");
-  for (int m = 0; m < members; ++m) {
-    if (!actors[m].net || misaligned(actors[m].net, 15)) {
-      std::snprintf(g_err, sizeof(g_err), "mg_rollout_qnet_many: member %d: net must be a 16-byte aligned packed Q-net", m);
-      return static_cast<int>(hipErrorInvalidValue);
-    }
-    if (opponent_mode == 3 && (!actors[m].opp_net || misaligned(actors[m].opp_net, 15))) {
-      std::snprintf(g_err, sizeof(g_err),
-                    "mg_rollout_qnet_many: member %d: opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net", m);
-      return static_cast<int>(hipErrorInvalidValue);
-    }
-  }
+  if (int e = check_qrollout_dims_mode(true, num_steps, out_dim, opponent_mode)) return e;
+  if (int e = check_qnet_actors(actors, members, opponent_mode)) return e;
   if (int e = check_traj(traj)) return e;
   if (n_member == 0 || num_steps == 0) return 0;
-  QRolloutMany A{};
-  A.R = make_rollout<QRollout>(params, state, traj, stats, 0, first_step, env_offset, n, num_steps, flags);
-  A.R.out_dim = out_dim;
-  A.R.fin = finish_bound(*params);
-  A.n_member = n_member;
-  A.blocks_per_member = static_cast<int32_t>(grid_blocks(n_member, kQWsEnvs));
-  A.members = members;
-  for (int m = 0; m < members; ++m)
-    A.mem[m] = QMember{static_cast<const uint8_t*>(actors[m].net),
-                       opponent_mode == 3 ? static_cast<const uint8_t*>(actors[m].opp_net) : nullptr, actors[m].seed,
-                       actors[m].greedy_threshold, actors[m].opp_greedy_threshold};
-  const bool checked = out_dim > MG_NUM_ACTIONS;
-  void (*const kernel)(QRolloutMany) =
-      opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true, true> : qnet_rollout_ws_kernel<0, false, true>)
-      : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true, true> : qnet_rollout_ws_kernel<1, false, true>)
-      : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true, true>
-                           : qnet_rollout_ws_kernel<3, true, true>;
-  launch(kernel, static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kQWsThreads,
+  QRollout R = make_rollout<QRollout>(params, state, traj, stats, 0, first_step, env_offset, n, num_steps, flags);
+  R.out_dim = out_dim, R.fin = finish_bound(*params);
+  const QRolloutMany A = make_qrollout_many(R, n_member, actors, members, opponent_mode);
+  launch(qnet_rollout_instance<true>(opponent_mode, out_dim > MG_NUM_ACTIONS),
+         static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kQWsThreads,
          static_cast<hipStream_t>(stream), A);
   return finish_launch("mg_rollout_qnet_many");
 }
@@ -350,129 +309,27 @@ int mg_rollout_hdqn(const mg_params* params, const mg_state* state, const mg_tra
   return finish_launch("mg_rollout_hdqn");
 }
 
-size_t mg_replay_scratch_bytes(int64_t n, int32_t num_steps) {
-  if (n <= 0 || num_steps <= 0) return 0;
-  const int64_t nb = ((n + kRBlock - 1) / kRBlock) * num_steps;
-  const int64_t ng = replay_groups(nb);
-  return static_cast<size_t>((8 + ng * 8 + nb * 4 + ng * 4 + 7) & ~int64_t{7});
-}
+size_t mg_replay_scratch_bytes(int64_t n, int32_t num_steps) { return replay_scratch_bytes(n, num_steps); }
 
 int mg_replay_store(float* rows, uint64_t* counter, int64_t capacity, int32_t row_floats,
                     const mg_transitions* tr, int64_t n, int32_t num_steps, int32_t skip_ego_won,
                     void* scratch, size_t scratch_bytes, void* stream) {
-  if (!rows || !counter || !tr) return fail(hipErrorInvalidValue, "%s", "mg_replay_store: NULL pointer");
-  if (capacity < 1) return fail(hipErrorInvalidValue, "%s", "mg_replay_store: capacity < 1");
-  if (row_floats != (tr->goal ? kRowGoal : kRow) || (tr->goal != nullptr) != (tr->next_goal != nullptr))
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_replay_store: row_floats must be 22, or 24 with both goal and next_goal set");
-  if (tr->meta_goal && (tr->goal || !tr->reward || !tr->won_mask))
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_replay_store: meta_goal (Goal_DQN rows) needs reward and won_mask (no_break) and no goal");
-  if (n < 0 || num_steps < 0) return fail(hipErrorInvalidValue, "%s", "mg_replay_store: n < 0 or num_steps < 0");
-  if (n == 0 || num_steps == 0) return 0;
-  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
-    return fail(hipErrorInvalidValue, "%s", "mg_replay_store: obs_first, obs, a1 (or flags) and rew are required");
-  if (misaligned(rows, 7) || misaligned(tr->obs_first, 7) || misaligned(tr->obs, 7) ||
-      misaligned(tr->final_obs, 7) || misaligned(tr->rew, 7) || misaligned(scratch, 7))
-    return fail(hipErrorInvalidValue, "%s", "mg_replay_store: float buffers and scratch must be 8-byte aligned");
-  if (misaligned(tr->goal, 3) || misaligned(tr->next_goal, 3) || misaligned(tr->reward, 3))
-    return fail(hipErrorInvalidValue, "%s", "mg_replay_store: goal, next_goal and reward must be 4-byte aligned");
-  const int64_t nbx = (n + kRBlock - 1) / kRBlock;
-  const int64_t nb = nbx * num_steps;
-  if (nbx > 0x7fffffff || replay_groups(nb) > 0x7fffffff)
-    return fail(hipErrorInvalidValue, "%s", "mg_replay_store: n * num_steps exceeds the grid limit");
-  if (!scratch || scratch_bytes < mg_replay_scratch_bytes(n, num_steps))
-    return fail(hipErrorInvalidValue, "%s", "mg_replay_store: scratch smaller than mg_replay_scratch_bytes(n, num_steps)");
-  const unsigned chunks = static_cast<unsigned>((num_steps + kRTChunk - 1) / kRTChunk);
-  if (chunks > 65535) return fail(hipErrorInvalidValue, "%s", "mg_replay_store: num_steps too large");
-  ReplayIn R{};
-  R.X = *tr;
-  R.n = n;
-  R.words = (n + 63) >> 6;
-  R.nbx = nbx;
-  R.nb = nb;
-  R.T = num_steps;
-  R.skip_won = tr->meta_goal ? 1 : skip_ego_won;  // Goal_DQN rows: keep the steps that broke
-  const ReplayScratch S = replay_scratch(scratch, nb);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(replay_scan_kernel, dim3(static_cast<unsigned>(replay_groups(nb))), dim3(64), 0, st,
-                     R, S);
-  hipLaunchKernelGGL(replay_group_scan_kernel, dim3(1), dim3(64), 0, st, S, replay_groups(nb), counter);
-  auto write_kernel = replay_write_kernel<1>;  // rows with goal and next_goal
-  if (!tr->goal) write_kernel = tr->meta_goal ? replay_write_kernel<2> : replay_write_kernel<0>;
-  hipLaunchKernelGGL(write_kernel, dim3(static_cast<unsigned>(nbx), chunks), dim3(kRBlock), 0, st, R, S, counter,
-                     rows, capacity);
-  return finish_launch("mg_replay_store");
+  const ReplayStore C{&rows, &counter, 1, capacity, row_floats, tr, n, num_steps, skip_ego_won, scratch, scratch_bytes};
+  if (int e = check_replay_store("mg_replay_store", C, false)) return e;
+  return replay_store_device<false>("mg_replay_store", C, static_cast<hipStream_t>(stream));
 }
 
 size_t mg_replay_scratch_many_bytes(int64_t n_member, int32_t num_steps, int32_t members) {
-  if (members < 1 || members > 64) return 0;
-  return static_cast<size_t>(members) * mg_replay_scratch_bytes(n_member, num_steps);
+  return members_ok(members) ? static_cast<size_t>(members) * replay_scratch_bytes(n_member, num_steps) : 0;
 }
 
 int mg_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
                          int32_t row_floats, const mg_transitions* tr, int64_t n_member, int32_t num_steps,
                          int32_t skip_ego_won, void* scratch, size_t scratch_bytes, void* stream) {
-  const char* const who = "mg_replay_store_many: %s";
-  if (members < 1 || members > 64) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
-  if (!rows || !counters || !tr) return fail(hipErrorInvalidValue, who, "NULL pointer");
-  for (int m = 0; m < members; ++m) {
-    if (!rows[m] || !counters[m]) return fail(hipErrorInvalidValue, who, "NULL pointer (a member's rows or counter)");
-    if (misaligned(rows[m], 7) || misaligned(counters[m], 7))
-      return fail(hipErrorInvalidValue, who, "every member's rows and counter must be 8-byte aligned");
-    for (int k = 0; k < m; ++k)
-      if (rows[k] == rows[m] || counters[k] == counters[m])
-        return fail(hipErrorInvalidValue, who,
-                    "a ring is listed twice (two members' appends to one ring have no defined order)");
-  }
-  if (capacity < 1) return fail(hipErrorInvalidValue, who, "capacity < 1");
-  if (row_floats != kRow || tr->goal || tr->next_goal || tr->meta_goal)
-    return fail(hipErrorInvalidValue, who, "22-float rows only: row_floats must be 22 and goal, next_goal, meta_goal NULL");
-  if (n_member < 0 || num_steps < 0) return fail(hipErrorInvalidValue, who, "n_member < 0 or num_steps < 0");
-  if (n_member % 64 != 0)
-    return fail(hipErrorInvalidValue, who,
-                "n_member must be a multiple of 64 (a member's won bits begin a word of the mask)");
-  if (n_member == 0 || num_steps == 0) return 0;
-  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
-    return fail(hipErrorInvalidValue, who, "obs_first, obs, a1 (or flags) and rew are required");
-  if (misaligned(tr->obs_first, 7) || misaligned(tr->obs, 7) || misaligned(tr->final_obs, 7) ||
-      misaligned(tr->rew, 7) || misaligned(tr->won_mask, 7) || misaligned(scratch, 7))
-    return fail(hipErrorInvalidValue, who, "float buffers, won_mask and scratch must be 8-byte aligned");
-  if (misaligned(tr->reward, 3)) return fail(hipErrorInvalidValue, who, "reward must be 4-byte aligned");
-  const int64_t nbx = (n_member + kRBlock - 1) / kRBlock;
-  const int64_t nb = nbx * num_steps;
-  if (nbx > 0x7fffffff || replay_groups(nb) > 0x7fffffff)
-    return fail(hipErrorInvalidValue, who, "n_member * num_steps exceeds the grid limit");
-  if (!scratch || scratch_bytes < mg_replay_scratch_many_bytes(n_member, num_steps, members))
-    return fail(hipErrorInvalidValue, who,
-                "scratch smaller than mg_replay_scratch_many_bytes(n_member, num_steps, members)");
-  const unsigned chunks = static_cast<unsigned>((num_steps + kRTChunk - 1) / kRTChunk);
-  if (chunks > 65535) return fail(hipErrorInvalidValue, who, "num_steps too large");
-  ReplayMany A{};
-  A.X = *tr;
-  A.n = n_member;
-  A.N = n_member * members;
-  A.words = (A.N + 63) >> 6;
-  A.nbx = nbx;
-  A.nb = nb;
-  A.T = num_steps;
-  A.skip_won = skip_ego_won;
-  A.scratch_stride = static_cast<int64_t>(mg_replay_scratch_bytes(n_member, num_steps));
-  A.scratch = static_cast<uint8_t*>(scratch);
-  A.cap = capacity;
-  A.ng = replay_groups(nb);
-  for (int m = 0; m < members; ++m) {
-    A.ring[m] = rows[m];
-    A.counter[m] = counters[m];
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned M = static_cast<unsigned>(members);
-  hipLaunchKernelGGL(replay_scan_many_kernel, dim3(static_cast<unsigned>(A.ng), M), dim3(64), 0, st, A);
-  hipLaunchKernelGGL(replay_group_scan_many_kernel, dim3(M), dim3(64), 0, st, A);
-  // the member instance reads ring, counter and scratch from A: its other four arguments are unused
-  hipLaunchKernelGGL((replay_write_kernel<0, true>), dim3(static_cast<unsigned>(nbx), chunks, M), dim3(kRBlock), 0, st,
-                     A, ReplayScratch{}, static_cast<const uint64_t*>(nullptr), static_cast<float*>(nullptr), int64_t{0});
-  return finish_launch("mg_replay_store_many");
+  const ReplayStore C{rows, counters, members, capacity, row_floats, tr, n_member, num_steps, skip_ego_won, scratch,
+                      scratch_bytes};
+  if (int e = check_replay_store("mg_replay_store_many", C, true)) return e;
+  return replay_store_device<true>("mg_replay_store_many", C, static_cast<hipStream_t>(stream));
 }
 
 int mg_replay_sample(const float* rows, const uint64_t* counter, int64_t capacity,
@@ -671,7 +528,7 @@ int mg_host_dqn_learn_many(float* learners, mg_dqn_member* member, int32_t membe
                                out_dim, batch, num_updates, filled_only, loss_out, rows_out, nullptr, 0, scratch,
                                scratch_bytes))
     return e;
-  LearnMember table[kLMaxMembers];
+  LearnMember table[kMaxMembers];
   for (int m = 0; m < members; ++m) table[m] = learn_member_entry(member[m]);
   LearnMany Q =
       make_learn_many(learners, table, member, members, capacity, in_dim, out_dim, batch, filled_only, scratch);

@@ -20,6 +20,7 @@ namespace {
 // (profiles/r01, profiles/r02/ab) was removed from the product source once it lost.
 constexpr int kBlock = 256;  // 4 waves of 64 (128 and 512 measured within 0.8 %)
 constexpr int kObs = MG_OBS_DIM;
+constexpr int kMaxMembers = 64;  // of one call: entries in the kernel argument, bits of the learner's target-copy mask
 
 // The step's functions compile for the host as well: the CPU single-env path (mg_host_step,
 // BASELINE config 1, scripts/human_player.py's 20 Hz loop on a machine without a GPU) runs this

@@ -97,6 +97,14 @@ int check_net_dims(const char* what, int32_t in_dim, int32_t out_dim) {
   return static_cast<int>(hipErrorInvalidValue);
 }
 
+bool members_ok(int32_t members) { return members >= 1 && members <= kMaxMembers; }
+
+// a refusal that names the member it is about
+int fail_member(const char* what, int m, const char* text) {
+  std::snprintf(g_err, sizeof(g_err), "%s: member %d: %s", what, m, text);
+  return static_cast<int>(hipErrorInvalidValue);
+}
+
 int finish_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

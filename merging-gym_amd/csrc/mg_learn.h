@@ -172,8 +172,6 @@ MG_HD LearnBwd learn_bwd_layer(const Learn& L, int layer) {
 MG_HD void learn_adam_at(const Learn& L, int64_t i) { learn_adam(L.eval[i], L.m[i], L.v[i], L.g[i], L.A); }
 
 // ---------------------------------------------------------------------------- the members of a call
-constexpr int kLMaxMembers = 64;  // one bit each in the target-copy mask
-
 // What a member keeps for all its updates: one entry of the device-resident member table
 // (mg_dqn_learn_many_init writes it once), or for the lone learner the entry LearnMany carries.
 struct LearnMember {
@@ -197,9 +195,9 @@ struct LearnMany {
   int32_t filled_only, in, out, B, members;
   float inv_b, two_inv_b;
   uint64_t sync;  // bit m: member m's target copy is due before this update
-  uint64_t draw[kLMaxMembers];
-  float step[kLMaxMembers];
-  float bc2s[kLMaxMembers];
+  uint64_t draw[kMaxMembers];
+  float step[kMaxMembers];
+  float bc2s[kMaxMembers];
   LearnMember one;  // last: the fields above keep the offsets the table's kernels read them at
 };
 static_assert(sizeof(LearnMany) <= 1200, "the by-value kernel argument stays well inside HIP's 4096 bytes");
@@ -352,13 +350,6 @@ int check_learn(const char* what, const float* learner, const float* rows, const
     return fail(hipErrorInvalidValue, "%s: scratch smaller than mg_dqn_learn_scratch_bytes(batch, in_dim, out_dim)",
                 what);
   return 0;
-}
-
-inline bool members_ok(int32_t members) { return members >= 1 && members <= kLMaxMembers; }
-
-inline int fail_member(const char* what, int m, const char* text) {
-  std::snprintf(g_err, sizeof(g_err), "%s: member %d: %s", what, m, text);
-  return static_cast<int>(hipErrorInvalidValue);
 }
 
 // What mg_dqn_learn_many_init, mg_dqn_learn_many and mg_host_dqn_learn_many refuse of the member list.

@@ -1,5 +1,6 @@
 // mg_replay.h -- the DQN replay ring: ReplayIn, ReplayScratch, the scan, write and sample kernels, counter_add_kernel,
-// and the store with the member in the grid (ReplayMany).
+// the store with the member in the grid (ReplayMany), and the host side of a store: the one call struct, check
+// and driver of mg_replay_store and mg_replay_store_many.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -7,6 +8,7 @@
 
 #include "mg_common.h"
 #include "mg_env.h"
+#include "mg_launch.h"
 
 namespace {
 
@@ -184,8 +186,8 @@ struct ReplayMany : ReplayIn {  // X: the whole batch; n = n_member; words = cei
   uint8_t* scratch;
   int64_t cap;
   int64_t ng;              // replay_groups(nb)
-  float* ring[64];
-  uint64_t* counter[64];
+  float* ring[kMaxMembers];
+  uint64_t* counter[kMaxMembers];
   __device__ int64_t stride() const { return N; }
   __device__ int64_t col0() const { return static_cast<int64_t>(blockIdx.z) * n; }  // the write kernel's grid
   __device__ ReplayScratch member_scratch(int m) const {
@@ -193,20 +195,6 @@ struct ReplayMany : ReplayIn {  // X: the whole batch; n = n_member; words = cei
   }
 };
 static_assert(sizeof(ReplayMany) <= 4096, "HIP's kernel argument limit");
-
-// What a block of replay_write_kernel takes from its other arguments (lone), or from its member's entries.
-__device__ __forceinline__ const ReplayScratch& replay_view_scratch(const ReplayIn&, const ReplayScratch& S) { return S; }
-__device__ __forceinline__ const uint64_t* replay_view_counter(const ReplayIn&, const uint64_t* c) { return c; }
-__device__ __forceinline__ float* replay_view_rows(const ReplayIn&, float* rows) { return rows; }
-__device__ __forceinline__ int64_t replay_view_cap(const ReplayIn&, int64_t cap) { return cap; }
-__device__ __forceinline__ ReplayScratch replay_view_scratch(const ReplayMany& A, const ReplayScratch&) {
-  return A.member_scratch(blockIdx.z);
-}
-__device__ __forceinline__ const uint64_t* replay_view_counter(const ReplayMany& A, const uint64_t*) {
-  return A.counter[blockIdx.z];
-}
-__device__ __forceinline__ float* replay_view_rows(const ReplayMany& A, float*) { return A.ring[blockIdx.z]; }
-__device__ __forceinline__ int64_t replay_view_cap(const ReplayMany& A, int64_t) { return A.cap; }
 
 __global__ __launch_bounds__(64) void replay_scan_many_kernel(const ReplayMany A) {  // grid (groups, members)
   replay_scan_group(A, A.member_scratch(blockIdx.y), blockIdx.x, static_cast<int64_t>(blockIdx.y) * A.n);
@@ -225,10 +213,11 @@ template <int KIND, bool MANY = false>
 __global__ __launch_bounds__(kRBlock) void replay_write_kernel(const std::conditional_t<MANY, ReplayMany, ReplayIn> R,
                                                                const ReplayScratch S1, const uint64_t* counter1,
                                                                float* rows1, int64_t cap1) {
-  decltype(auto) S = replay_view_scratch(R, S1);
-  const uint64_t* counter = replay_view_counter(R, counter1);
-  float* rows = replay_view_rows(R, rows1);
-  const int64_t cap = replay_view_cap(R, cap1);
+  ReplayScratch S = S1;
+  const uint64_t* counter = counter1;
+  float* rows = rows1;
+  int64_t cap = cap1;
+  if constexpr (MANY) S = R.member_scratch(blockIdx.z), counter = R.counter[blockIdx.z], rows = R.ring[blockIdx.z], cap = R.cap;
   constexpr bool GOAL = KIND == 1;
   constexpr bool META = KIND == 2;
   constexpr int kRow = GOAL ? kRowGoal : 2 * kObs + 2;  // floats per row
@@ -348,5 +337,107 @@ __global__ __launch_bounds__(kBlock) void replay_sample_kernel(const float* rows
 // memory_counter += k for the stores that keep every transition, so need no scan (the fused goal ring, Rainbow's
 // rows): launched behind the store, after every thread of it has read the old counter; the stream orders it
 __global__ void counter_add_kernel(uint64_t* counter, uint64_t k) { *counter += k; }
+
+// ============================================================================ the host side of a call
+// mg_replay_store is mg_replay_store_many's list of one ring: both fill a ReplayStore, check_replay_store refuses
+// what either refuses, in that entry point's order and words, and replay_store_device<MANY> launches.
+
+// the bytes replay_scratch carves for one ring's store (a member store takes `members` of them back to back)
+inline size_t replay_scratch_bytes(int64_t n, int32_t num_steps) {
+  if (n <= 0 || num_steps <= 0) return 0;
+  const int64_t nb = ((n + kRBlock - 1) / kRBlock) * num_steps;
+  const int64_t ng = replay_groups(nb);
+  return static_cast<size_t>((8 + ng * 8 + nb * 4 + ng * 4 + 7) & ~int64_t{7});
+}
+
+struct ReplayStore {  // in the order of mg_replay_store_many's arguments
+  float* const* ring;  // `members` rings and their counters (the lone call: the addresses of its two arguments)
+  uint64_t* const* counter;
+  int32_t members;
+  int64_t capacity;
+  int32_t row_floats;
+  const mg_transitions* tr;
+  int64_t n;  // envs of one member
+  int32_t T, skip_won;
+  void* scratch;
+  size_t scratch_bytes;
+  int64_t nbx() const { return (n + kRBlock - 1) / kRBlock; }  // a member's write blocks per step,
+  int64_t nb() const { return nbx() * T; }                     // write blocks,
+  int64_t ng() const { return replay_groups(nb()); }           // and scan groups
+  int64_t chunks() const { return (int64_t{T} + kRTChunk - 1) / kRTChunk; }
+};
+
+// One walk for both: the member call (`many`) adds the checks of its lists, takes 22-float rows only and checks the
+// won mask's alignment. A call with nothing to store returns 0 midway, as replay_store_device does at once.
+int check_replay_store(const char* who, const ReplayStore& C, bool many) {
+  const auto bad = [who](const char* fmt) { return fail(hipErrorInvalidValue, fmt, who); };
+  if (many && !members_ok(C.members)) return bad("%s: need 1 <= members <= 64");
+  if (!C.ring || !C.counter || !C.tr || (!many && (!C.ring[0] || !C.counter[0]))) return bad("%s: NULL pointer");
+  for (int m = 0; many && m < C.members; ++m) {
+    if (!C.ring[m] || !C.counter[m]) return bad("%s: NULL pointer (a member's rows or counter)");
+    if (misaligned(C.ring[m], 7) || misaligned(C.counter[m], 7))
+      return bad("%s: every member's rows and counter must be 8-byte aligned");
+    for (int k = 0; k < m; ++k)
+      if (C.ring[k] == C.ring[m] || C.counter[k] == C.counter[m])
+        return bad("%s: a ring is listed twice (two members' appends to one ring have no defined order)");
+  }
+  if (C.capacity < 1) return bad("%s: capacity < 1");
+  const mg_transitions& X = *C.tr;
+  if (many && (C.row_floats != kRow || X.goal || X.next_goal || X.meta_goal))
+    return bad("%s: 22-float rows only: row_floats must be 22 and goal, next_goal, meta_goal NULL");
+  if (C.row_floats != (X.goal ? kRowGoal : kRow) || (X.goal != nullptr) != (X.next_goal != nullptr))
+    return bad("%s: row_floats must be 22, or 24 with both goal and next_goal set");
+  if (X.meta_goal && (X.goal || !X.reward || !X.won_mask))
+    return bad("%s: meta_goal (Goal_DQN rows) needs reward and won_mask (no_break) and no goal");
+  if (C.n < 0 || C.T < 0) return bad(many ? "%s: n_member < 0 or num_steps < 0" : "%s: n < 0 or num_steps < 0");
+  if (many && C.n % 64 != 0)
+    return bad("%s: n_member must be a multiple of 64 (a member's won bits begin a word of the mask)");
+  if (C.n == 0 || C.T == 0) return 0;
+  if (!X.obs_first || !X.obs || !(X.a1 || X.flags) || !X.rew)
+    return bad("%s: obs_first, obs, a1 (or flags) and rew are required");
+  if ((many ? misaligned(X.won_mask, 7) : misaligned(C.ring[0], 7)) || misaligned(X.obs_first, 7) ||
+      misaligned(X.obs, 7) || misaligned(X.final_obs, 7) || misaligned(X.rew, 7) || misaligned(C.scratch, 7))
+    return bad(many ? "%s: float buffers, won_mask and scratch must be 8-byte aligned"
+                    : "%s: float buffers and scratch must be 8-byte aligned");
+  if (misaligned(X.goal, 3) || misaligned(X.next_goal, 3) || misaligned(X.reward, 3))  // member call: no goals
+    return bad(many ? "%s: reward must be 4-byte aligned" : "%s: goal, next_goal and reward must be 4-byte aligned");
+  if (C.nbx() > 0x7fffffff || C.ng() > 0x7fffffff)
+    return bad(many ? "%s: n_member * num_steps exceeds the grid limit" : "%s: n * num_steps exceeds the grid limit");
+  if (!C.scratch || C.scratch_bytes < static_cast<size_t>(C.members) * replay_scratch_bytes(C.n, C.T))
+    return bad(many ? "%s: scratch smaller than mg_replay_scratch_many_bytes(n_member, num_steps, members)"
+                    : "%s: scratch smaller than mg_replay_scratch_bytes(n, num_steps)");
+  return C.chunks() > 65535 ? bad("%s: num_steps too large") : 0;
+}
+
+// A checked store's three launches: the scan, the group scan, the write, the member in each grid's last dimension;
+// the lone call is the batch of one member (N = n: the same won-mask words). A template, so that each entry point
+// first names its write instances where it stands: they come out in the code object in the order of first naming.
+template <bool MANY>
+int replay_store_device(const char* who, const ReplayStore& C, hipStream_t st) {
+  if (C.n == 0 || C.T == 0) return 0;
+  const unsigned nbx = static_cast<unsigned>(C.nbx()), ng = static_cast<unsigned>(C.ng());
+  const unsigned chunks = static_cast<unsigned>(C.chunks()), M = static_cast<unsigned>(C.members);
+  const int64_t N = C.n * C.members;  // below: Goal_DQN rows (meta_goal) keep the steps that broke
+  const ReplayIn R{*C.tr, C.n, (N + 63) >> 6, C.nbx(), C.nb(), C.T, C.tr->meta_goal ? 1 : C.skip_won};
+  if constexpr (!MANY) {
+    const ReplayScratch S = replay_scratch(C.scratch, C.nb());
+    hipLaunchKernelGGL(replay_scan_kernel, dim3(ng), dim3(64), 0, st, R, S);
+    hipLaunchKernelGGL(replay_group_scan_kernel, dim3(1), dim3(64), 0, st, S, C.ng(), C.counter[0]);
+    auto write_kernel = replay_write_kernel<1>;  // rows with goal and next_goal
+    if (!R.X.goal) write_kernel = R.X.meta_goal ? replay_write_kernel<2> : replay_write_kernel<0>;
+    hipLaunchKernelGGL(write_kernel, dim3(nbx, chunks), dim3(kRBlock), 0, st, R, S, C.counter[0], C.ring[0],
+                       C.capacity);
+  } else {
+    ReplayMany A{R, N, static_cast<int64_t>(replay_scratch_bytes(C.n, C.T)), static_cast<uint8_t*>(C.scratch),
+                 C.capacity, C.ng()};
+    std::copy(C.ring, C.ring + C.members, A.ring);
+    std::copy(C.counter, C.counter + C.members, A.counter);
+    hipLaunchKernelGGL(replay_scan_many_kernel, dim3(ng, M), dim3(64), 0, st, A);
+    hipLaunchKernelGGL(replay_group_scan_many_kernel, dim3(M), dim3(64), 0, st, A);
+    hipLaunchKernelGGL((replay_write_kernel<0, true>), dim3(nbx, chunks, M), dim3(kRBlock), 0, st, A, ReplayScratch{},
+                       static_cast<const uint64_t*>(nullptr), static_cast<float*>(nullptr), int64_t{0});
+  }
+  return finish_launch(who);
+}
 
 }  // namespace

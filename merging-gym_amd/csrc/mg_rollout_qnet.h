@@ -1,5 +1,6 @@
 // mg_rollout_qnet.h -- config 5, the Q-net policy rollout: FinishBound, QRollout, qnet_rollout_ws_kernel, and
-// the same kernel with the member in the grid (QRolloutMany, QMemberRollout, the MANY instances).
+// the same kernel with the member in the grid (QRolloutMany, QMemberRollout, the MANY instances), and the host
+// side of mg_rollout_qnet and mg_rollout_qnet_many: their shared checks, the launch's fill, the choice of instance.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -7,6 +8,7 @@
 
 #include "mg_common.h"
 #include "mg_env.h"
+#include "mg_launch.h"
 #include "mg_qnet.h"
 #include "mg_stats.h"
 #include "mg_wave_out.h"
@@ -114,7 +116,6 @@ struct QRollout {
 // ---- the member in the grid (mg_rollout_qnet_many; the kernel's MANY instances): one batch of members * n_member envs, member m
 // owning envs [m n_member, (m + 1) n_member) and acting with its own net, opponent net, seed and
 // thresholds. The kernel argument carries the shared launch and the members' scalars.
-constexpr int kQMaxMembers = 64;
 struct QMember {
   const uint8_t* net;
   const uint8_t* opp_net;
@@ -127,7 +128,7 @@ struct QRolloutMany {
   int64_t n_member;  // a multiple of 64: no won-mask word spans two members
   int32_t blocks_per_member;  // ceil(n_member / kQWsEnvs)
   int32_t members;
-  QMember mem[kQMaxMembers];
+  QMember mem[kMaxMembers];
 };
 static_assert(sizeof(QRolloutMany) <= 4096, "HIP's kernel argument limit");
 
@@ -751,6 +752,56 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
     if (live0[j]) store_env(R.S, base + la, e0[j]);
     if (live1[j]) store_env(R.S, base + kHalf + la, e1[j]);
   }
+}
+
+// ============================================================================ the host side of a call
+// What mg_rollout_qnet and mg_rollout_qnet_many share. Each keeps its own order of checks (the lone call looks at
+// its net before out_dim, the member call at every member's nets after the mode): the pieces are shared, not the walk.
+// The launch's fill is make_rollout (mg_launch.h) and two more fields, out_dim and fin, set where it is made.
+
+// num_steps and out_dim, then the mode: neighbours in both orders. The member call's texts carry its name.
+int check_qrollout_dims_mode(bool many, int32_t num_steps, int32_t out_dim, int32_t opponent_mode) {
+  const char* const who = many ? "mg_rollout_qnet_many: %s" : "%s";
+  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
+    return fail(hipErrorInvalidValue, who, "need num_steps >= 0 and 1 <= out_dim <= 8");
+  if (opponent_mode < 0 || opponent_mode > 3)
+    return fail(hipErrorInvalidValue, who,
+                many ? "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (each member's opp_net)"
+                     : "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (opp_net)");
+  return 0;
+}
+
+// Every member's net, and in mode 3 its opponent's: member by member, so member 0's opp_net before member 1's net.
+int check_qnet_actors(const mg_qnet_actor* actors, int32_t members, int32_t opponent_mode) {
+  for (int m = 0; m < members; ++m) {
+    if (!actors[m].net || misaligned(actors[m].net, 15))
+      return fail_member("mg_rollout_qnet_many", m, "net must be a 16-byte aligned packed Q-net");
+    if (opponent_mode == 3 && (!actors[m].opp_net || misaligned(actors[m].opp_net, 15)))
+      return fail_member("mg_rollout_qnet_many", m, "opponent_mode 3 needs opp_net, a 16-byte aligned packed Q-net");
+  }
+  return 0;
+}
+
+// The member call's argument: the launch (n = members * n_member; seed, nets, thresholds unused), the entries.
+QRolloutMany make_qrollout_many(const QRollout& R, int64_t n_member, const mg_qnet_actor* actors, int32_t members,
+                                int32_t opponent_mode) {
+  QRolloutMany A{R, n_member, static_cast<int32_t>(grid_blocks(n_member, kQWsEnvs)), members};
+  for (int m = 0; m < members; ++m)
+    A.mem[m] = QMember{static_cast<const uint8_t*>(actors[m].net),
+                       opponent_mode == 3 ? static_cast<const uint8_t*>(actors[m].opp_net) : nullptr, actors[m].seed,
+                       actors[m].greedy_threshold, actors[m].opp_greedy_threshold};
+  return A;
+}
+
+// The instance for a launch. checked: an argmax may name an action past action_dict (out_dim > 5); a net opponent's
+// instances are always checked. They come out in the code object in the order of first naming: the lone call's.
+template <bool MANY>
+auto qnet_rollout_instance(int32_t opponent_mode, bool checked)
+    -> void (*)(std::conditional_t<MANY, QRolloutMany, QRollout>) {
+  return opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true, MANY> : qnet_rollout_ws_kernel<0, false, MANY>)
+         : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true, MANY> : qnet_rollout_ws_kernel<1, false, MANY>)
+         : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true, MANY>
+                              : qnet_rollout_ws_kernel<3, true, MANY>;
 }
 
 }  // namespace

@@ -5,6 +5,22 @@ DQNLearner and DQNPopulation share of a DQN net's handling (DQNNets)."""
 from ._device import U64, cuda_device, raw_stream, require_gpu
 from .policy import QNet
 
+MAX_MEMBERS = 64  # the members one call takes: actors of a rollout, rings of a store, learners of a population
+
+
+def per_member(value, members, name, pair=False):
+    """`value` for every member: a scalar (a pair, for betas) applied to all, or a sequence of `members`."""
+    shared = not hasattr(value, "__len__") and not hasattr(value, "__iter__")
+    if pair:
+        value = list(value)
+        shared = len(value) == 2 and not hasattr(value[0], "__len__")
+    if shared:
+        return [value] * members
+    value = list(value)
+    if len(value) != members:
+        raise ValueError(f"{name}: expected one value or {members}, got {len(value)}")
+    return value
+
 
 class RingBase:
     """[capacity, row] fp32 rows on the device; the position is a device counter, so stores are stream-ordered."""

@@ -36,6 +36,7 @@ import os
 import numpy as np
 
 from .. import spaces
+from .._base import MAX_MEMBERS, per_member
 from .._device import U64, cuda_device, ptr, raw_stream
 
 _OBS_DIM = 10
@@ -346,25 +347,37 @@ class MergeVecEnv:
         the swapped observation). Returns the same [T, N, ...] dict as rollout_random."""
         from ..policy import greedy_threshold
 
-        torch, nat = self._torch, self._nat
-        T, n = int(num_steps), self.num_envs
-        opp_net = None
-        if isinstance(opponent, str):
-            mode = {"none": 0, "uniform": 1, "self": 2}[opponent]
-        else:  # a QNet: the opponent's own DQN
-            mode, opp_net = 3, opponent
-            if opp_net.in_dim != _OBS_DIM or opp_net.out_dim != qnet.out_dim:
-                raise ValueError("the opponent's net needs in_dim 10 and the ego net's out_dim")
+        mode, (opp_net,) = self._opponent(opponent, qnet.out_dim)
         if qnet.in_dim != _OBS_DIM:
             raise ValueError("the fused rollout feeds the 10-value observation: the net needs in_dim 10")
+        return self._qnet_rollout("mg_rollout_qnet", int(num_steps), first_step, final_observation, won_mask,
+                                  lambda traj, k0, T: self._nat.lib.mg_rollout_qnet(
+                                      self._p_ref, self._s_ref, traj, self._st_ref, self.num_envs, self.env_offset,
+                                      seed & U64, k0, T, qnet.packed.data_ptr(), qnet.out_dim,
+                                      greedy_threshold(episilo), mode, greedy_threshold(opp_episilo),
+                                      None if opp_net is None else opp_net.packed.data_ptr(), self._flags,
+                                      self._stream()))
+
+    @staticmethod
+    def _opponent(opponent, out_dim, members=None):
+        """A Q-net rollout's `opponent` as (opponent_mode, the opponents' nets): a mode for every ego net, or the
+        opponent's own QNet (members: a list of that many, one per member), of in_dim 10 and the ego's out_dim."""
+        if isinstance(opponent, str):
+            return {"none": 0, "uniform": 1, "self": 2}[opponent], [None] * (members or 1)
+        nets = [opponent] if members is None else list(opponent)
+        if len(nets) != (members or 1):
+            raise ValueError(f"opponent: expected a mode or {members} nets, got {len(nets)}")
+        if any(o.in_dim != _OBS_DIM or o.out_dim != out_dim for o in nets):
+            raise ValueError("the opponent's net needs in_dim 10 and the ego net's out_dim" if members is None else
+                             "the opponents' nets need in_dim 10 and the ego nets' out_dim")
+        return 3, nets
+
+    def _qnet_rollout(self, entry, T, first_step, final_observation, won_mask, call):
+        """What the Q-net rollouts do around their C entry point `call(traj, first step, T)`: the first step, the
+        trajectory buffers, the check of the return code, the step index moved on, the result."""
         k0 = self._step_idx if first_step is None else int(first_step)
         buf = self._traj(T, final_observation, won_mask)
-        rc = nat.lib.mg_rollout_qnet(
-            self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, n, self.env_offset,
-            seed & U64, k0 & U64, T, qnet.packed.data_ptr(), qnet.out_dim,
-            greedy_threshold(episilo), mode, greedy_threshold(opp_episilo),
-            None if opp_net is None else opp_net.packed.data_ptr(), self._flags, self._stream())
-        nat.check(rc, "mg_rollout_qnet")
+        self._nat.check(call(ctypes.byref(buf["_traj"]), k0 & U64, T), entry)
         self._step_idx = k0 + T
         return buf["_result"]
 
@@ -381,11 +394,10 @@ class MergeVecEnv:
         (replay.store_rollout_many appends it to M rings in place). The members' scalars travel in the kernel
         argument: a call allocates and synchronises nothing."""
         from ..policy import greedy_threshold
-        from ..population import MAX_MEMBERS, _per_member
 
         nat = self._nat
         qnets = list(qnets)
-        M, T = len(qnets), int(num_steps)
+        M = len(qnets)
         if not 1 <= M <= MAX_MEMBERS:
             raise ValueError(f"rollout_qnet_many takes 1..{MAX_MEMBERS} nets, got {M}")
         if self.num_envs % M or (self.num_envs // M) % 64:
@@ -396,30 +408,18 @@ class MergeVecEnv:
             raise ValueError("the nets of one launch share one out_dim")
         if any(q.in_dim != _OBS_DIM for q in qnets):
             raise ValueError("the fused rollout feeds the 10-value observation: the nets need in_dim 10")
-        opp_nets = [None] * M
-        if isinstance(opponent, str):
-            mode = {"none": 0, "uniform": 1, "self": 2}[opponent]
-        else:  # each member's own opponent net
-            mode, opp_nets = 3, list(opponent)
-            if len(opp_nets) != M:
-                raise ValueError(f"opponent: expected a mode or {M} nets, got {len(opp_nets)}")
-            if any(o.in_dim != _OBS_DIM or o.out_dim != out_dim for o in opp_nets):
-                raise ValueError("the opponents' nets need in_dim 10 and the ego nets' out_dim")
-        seeds = _per_member(seed, M, "seed")
-        eps, opp_eps = _per_member(episilo, M, "episilo"), _per_member(opp_episilo, M, "opp_episilo")
+        mode, opp_nets = self._opponent(opponent, out_dim, M)
+        seeds = per_member(seed, M, "seed")
+        eps, opp_eps = per_member(episilo, M, "episilo"), per_member(opp_episilo, M, "opp_episilo")
         actors = (nat.QnetActor * M)()
         for m in range(M):
             actors[m] = nat.QnetActor(qnets[m].packed.data_ptr(),
                                       None if opp_nets[m] is None else opp_nets[m].packed.data_ptr(),
                                       int(seeds[m]) & U64, greedy_threshold(eps[m]), greedy_threshold(opp_eps[m]))
-        k0 = self._step_idx if first_step is None else int(first_step)
-        buf = self._traj(T, final_observation, won_mask)
-        rc = nat.lib.mg_rollout_qnet_many(
-            self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, self.num_envs // M, M,
-            self.env_offset, k0 & U64, T, actors, out_dim, mode, self._flags, self._stream())
-        nat.check(rc, "mg_rollout_qnet_many")
-        self._step_idx = k0 + T
-        return buf["_result"]
+        return self._qnet_rollout("mg_rollout_qnet_many", int(num_steps), first_step, final_observation, won_mask,
+                                  lambda traj, k0, T: nat.lib.mg_rollout_qnet_many(
+                                      self._p_ref, self._s_ref, traj, self._st_ref, self.num_envs // M, M,
+                                      self.env_offset, k0, T, actors, out_dim, mode, self._flags, self._stream()))
 
     def member_summaries(self, members: int):
         """episode_summary() of each of `members` equal slices of the batch (rollout_qnet_many's members): a

@@ -20,25 +20,8 @@ member_state_dict(m) is that learner's state_dict() and loads into one, and back
 from __future__ import annotations
 
 from . import _native
-from ._base import DQNNets
+from ._base import MAX_MEMBERS, DQNNets, per_member
 from ._device import U64, cuda_device, ptr, raw_stream, require_gpu
-
-MAX_MEMBERS = 64
-
-
-def _per_member(value, members, name, pair=False):
-    """`value` for every member: a scalar (a pair, for betas) applied to all, or a sequence of `members`."""
-    shared = not hasattr(value, "__len__") and not hasattr(value, "__iter__")
-    if pair:
-        value = list(value)
-        shared = len(value) == 2 and not hasattr(value[0], "__len__")
-    if shared:
-        return [value] * members
-    value = list(value)
-    if len(value) != members:
-        raise ValueError(f"{name}: expected one value or {members}, got {len(value)}")
-    return value
-
 
 class DQNPopulation(DQNNets):
     def __init__(self, nets, rings, lr=0.01, gamma=0.9, batch_size: int = 128, target_period=100,
@@ -73,9 +56,9 @@ class DQNPopulation(DQNNets):
         one = int(lib.mg_dqn_learn_scratch_bytes(self.batch_size, self.in_dim, self.out_dim))
         if one == 0:
             raise ValueError("batch_size must be in 1..1024")
-        lrs, gammas, epss = (_per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
-        periods, seeds = _per_member(target_period, M, "target_period"), _per_member(seed, M, "seed")
-        pairs = _per_member(betas, M, "betas", pair=True)
+        lrs, gammas, epss = (per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
+        periods, seeds = per_member(target_period, M, "target_period"), per_member(seed, M, "seed")
+        pairs = per_member(betas, M, "betas", pair=True)
         self._members = (_native.DqnMember * M)()
         for m in range(M):
             self._members[m] = _native.DqnMember(

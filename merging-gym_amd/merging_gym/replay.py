@@ -27,7 +27,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _native
-from ._base import RingBase
+from ._base import MAX_MEMBERS, RingBase
 from ._device import ptr
 
 _OBS_DIM = 10
@@ -44,11 +44,22 @@ class ReplayRing(RingBase):
         self._sample_bufs = {}
 
     # ------------------------------------------------------------------ helpers
-    def _scratch_for(self, n, T):
-        need = int(_native.lib.mg_replay_scratch_bytes(n, T))
-        if self._scratch.numel() * 8 < need:
-            self._scratch = self._torch.empty((need + 7) // 8, dtype=self._torch.int64, device=self.device)
+    def _scratch_for(self, nbytes):
+        """The ring's scratch, grown to `nbytes` (the library's mg_replay_scratch*_bytes of the store)."""
+        if self._scratch.numel() * 8 < nbytes:
+            self._scratch = self._torch.empty((nbytes + 7) // 8, dtype=self._torch.int64, device=self.device)
         return self._scratch
+
+    def _batch_f32(self, T, n, obs_first, obs, rew, final_obs):
+        """The float tensors of a [T, n, ...] batch, as contiguous fp32 on the ring's device."""
+        return (self._f32(obs_first, (n, _OBS_DIM)), self._f32(obs, (T, n, _OBS_DIM)), self._f32(rew, (T, n, 2)),
+                None if final_obs is None else self._f32(final_obs, (T, n, _OBS_DIM)))
+
+    def _transitions(self, **tensors):
+        """mg_transitions of the named tensors (None or unnamed: absent); the ring keeps them alive until its next
+        store has been enqueued."""
+        self._keepalive = tuple(tensors.values())
+        return _native.Transitions(**{k: ptr(t) for k, t in tensors.items()})
 
     # ------------------------------------------------------------------ stores
     @property
@@ -75,18 +86,10 @@ class ReplayRing(RingBase):
                 raise ValueError("Goal_DQN rows need a plain ring, reward (ext_reward) and won_mask (no_break)")
             skip_ego_won = True
         a1 = torch.as_tensor(a1, device=self.device)
-        if a1.dim() == 1:  # one step
-            goal = None if goal is None else torch.as_tensor(goal, device=self.device)[None]
-            next_goal = None if next_goal is None else torch.as_tensor(next_goal, device=self.device)[None]
-            reward = None if reward is None else torch.as_tensor(reward, device=self.device)[None]
-            meta_goal = None if meta_goal is None else torch.as_tensor(meta_goal, device=self.device)[None]
-            a1 = a1[None]
-            obs = torch.as_tensor(obs, device=self.device)[None]
-            rew = torch.as_tensor(rew, device=self.device)[None]
-            done = None if done is None else torch.as_tensor(done, device=self.device)[None]
-            final_obs = None if final_obs is None else torch.as_tensor(final_obs, device=self.device)[None]
-            won_mask = None if won_mask is None else torch.as_tensor(won_mask, device=self.device)[None]
-            flags = None if flags is None else torch.as_tensor(flags, device=self.device)[None]
+        if a1.dim() == 1:  # one step: every [N, ...] tensor becomes [1, N, ...]
+            a1, obs, rew, done, final_obs, won_mask, flags, goal, next_goal, reward, meta_goal = (
+                None if t is None else torch.as_tensor(t, device=self.device)[None]
+                for t in (a1, obs, rew, done, final_obs, won_mask, flags, goal, next_goal, reward, meta_goal))
         T, n = a1.shape
         if flags is not None:
             flags = torch.as_tensor(flags, device=self.device)
@@ -97,11 +100,7 @@ class ReplayRing(RingBase):
             a1 = a1.to(torch.int8)
         if a1 is not None:
             a1 = a1.contiguous()
-        obs_first = self._f32(obs_first, (n, _OBS_DIM))
-        obs = self._f32(obs, (T, n, _OBS_DIM))
-        rew = self._f32(rew, (T, n, 2))
-        if final_obs is not None:
-            final_obs = self._f32(final_obs, (T, n, _OBS_DIM))
+        obs_first, obs, rew, final_obs = self._batch_f32(T, n, obs_first, obs, rew, final_obs)
         if goal is not None:
             goal, next_goal = self._f32(goal, (T, n)), self._f32(next_goal, (T, n))
         if reward is not None:
@@ -122,16 +121,14 @@ class ReplayRing(RingBase):
         elif skip_ego_won:
             raise ValueError("skip_ego_won needs the won_mask of the step(s) (main.py:209): roll out "
                              "with won_mask=True / MergeVecEnv(won_mask=True), or pass skip_ego_won=False")
-        tr = _native.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), ptr(a1), ptr(rew),
-                                 ptr(done), ptr(won_mask) if skip_ego_won else None, ptr(goal),
-                                 ptr(next_goal), ptr(reward), ptr(flags), ptr(meta_goal))
-        scratch = self._scratch_for(n, T)
+        tr = self._transitions(obs_first=obs_first, obs=obs, final_obs=final_obs, a1=a1, rew=rew, done=done,
+                               won_mask=won_mask if skip_ego_won else None, goal=goal, next_goal=next_goal,
+                               reward=reward, flags=flags, meta_goal=meta_goal)
+        scratch = self._scratch_for(int(_native.lib.mg_replay_scratch_bytes(n, T)))
         rc = _native.lib.mg_replay_store(
             self.memory.data_ptr(), self._counter.data_ptr(), self.capacity, self.row, ctypes.byref(tr), n,
             T, 1 if skip_ego_won else 0, scratch.data_ptr(), scratch.numel() * 8, self._stream())
         _native.check(rc, "mg_replay_store")
-        self._keepalive = (obs_first, obs, a1, rew, done, final_obs, won_mask, goal, next_goal, reward, flags,
-                           meta_goal)
 
     def store_rollout(self, obs_first, traj, skip_ego_won: bool = True, goal=None, next_goal=None,
                       reward=None):
@@ -212,8 +209,8 @@ def store_rollout_many(rings, obs_first, traj, skip_ego_won: bool = True):
     rollout's final_observation. Nothing is copied and nothing is synchronised."""
     rings = list(rings)
     M = len(rings)
-    if not 1 <= M <= 64:
-        raise ValueError(f"store_rollout_many takes 1..64 rings, got {M}")
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"store_rollout_many takes 1..{MAX_MEMBERS} rings, got {M}")
     r0 = rings[0]
     torch = r0._torch
     if any(r.goal for r in rings):
@@ -229,10 +226,7 @@ def store_rollout_many(rings, obs_first, traj, skip_ego_won: bool = True):
     T, N = int(flags.shape[0]), int(flags.shape[1])
     if N % M or (N // M) % 64:
         raise ValueError(f"N = {N} must be {M} slices of a multiple of 64 envs")
-    obs_first = r0._f32(obs_first, (N, _OBS_DIM))
-    obs = r0._f32(traj["obs"], (T, N, _OBS_DIM))
-    rew = r0._f32(traj["rew"], (T, N, 2))
-    final_obs = r0._f32(final_obs, (T, N, _OBS_DIM))
+    obs_first, obs, rew, final_obs = r0._batch_f32(T, N, obs_first, traj["obs"], traj["rew"], final_obs)
     won_mask = traj.get("won_mask")
     if skip_ego_won:
         if won_mask is None:
@@ -241,15 +235,12 @@ def store_rollout_many(rings, obs_first, traj, skip_ego_won: bool = True):
         if (won_mask.dtype != torch.int64 or tuple(won_mask.shape) != (T, (N + 63) // 64)
                 or not won_mask.is_contiguous() or won_mask.device != r0.device):
             raise ValueError(f"won_mask must be a contiguous [{T}, {(N + 63) // 64}] int64 tensor on {r0.device}")
-    tr = _native.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), None, ptr(rew), None,
-                             ptr(won_mask) if skip_ego_won else None, None, None, None, ptr(flags), None)
-    need = int(_native.lib.mg_replay_scratch_many_bytes(N // M, T, M))
-    if r0._scratch.numel() * 8 < need:
-        r0._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=r0.device)
+    tr = r0._transitions(obs_first=obs_first, obs=obs, final_obs=final_obs, rew=rew,
+                         won_mask=won_mask if skip_ego_won else None, flags=flags)
+    scratch = r0._scratch_for(int(_native.lib.mg_replay_scratch_many_bytes(N // M, T, M)))
     rows = (ctypes.c_void_p * M)(*(r.memory.data_ptr() for r in rings))
     counters = (ctypes.c_void_p * M)(*(r._counter.data_ptr() for r in rings))
     rc = _native.lib.mg_replay_store_many(rows, counters, M, r0.capacity, r0.row, ctypes.byref(tr), N // M, T,
-                                          1 if skip_ego_won else 0, r0._scratch.data_ptr(), r0._scratch.numel() * 8,
+                                          1 if skip_ego_won else 0, scratch.data_ptr(), scratch.numel() * 8,
                                           r0._stream())
     _native.check(rc, "mg_replay_store_many")
-    r0._keepalive = (obs_first, obs, rew, final_obs, won_mask, flags)
