@@ -994,6 +994,59 @@ int mg_host_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t nu
 int mg_rainbow_ndtri(const double* u, double* z, int64_t n, void* stream);
 int mg_host_rainbow_ndtri(const double* u, double* z, int64_t n);
 
+/* ---- A population of Rainbow learners in one set of launches (additive to ABI 21) -------------------
+ * Up to 64 independent Rainbow learners of one batch size and capacity trained by mg_rainbow_learn's seven
+ * launches per update, the member a grid dimension. Members share `batch` and `capacity`; each has its own
+ * learner block, replay rows and counter, minibatch seed, counters (first_update, first_draw) and
+ * hyperparameters (lr, gamma, betas, eps), given as an mg_dqn_member (hyper.target_period is not read, as in
+ * mg_rainbow_learn; two members may name the same rows and counter: learning only reads them).
+ *
+ *   learners  [members, mg_rainbow_learner_bytes() / 4] fp32, member m's block as mg_rainbow_learn takes it
+ *   table     mg_rainbow_learn_many_table_bytes(members) device bytes, 16-byte aligned, written by
+ *             mg_rainbow_learn_many_init from the member list: what does not change between updates (rows, counter,
+ *             seed, gamma, Adam's beta1, 1 - beta1, beta2, 1 - beta2, eps, each rounded to fp32 once as the lone call
+ *             rounds it). Write it again after any of these changes; the counters are not in it.
+ *   noise     [num_updates][members][2][1124] fp32: update u's factors of member m, current model then target,
+ *             mg_rainbow_learn's layout per member. mg_rainbow_noise_many fills it in one launch: element
+ *             (u, m, model, f) is element (u, model, f) of mg_rainbow_noise(noise_seed[m], first_update[m], ...);
+ *             noise_seed and first_update are HOST arrays [members] (they travel in the kernel argument).
+ *   loss_out [U][M], rows_out [U][M][B][24], proj_out [U][M][B][51], grads_out [U][M][58884]: optional (NULL).
+ *   packed_out  optional: member m's acting net (mg_rainbow_pack's layout of its current model's effective
+ *             weights) at packed_out + m * packed_stride; packed_stride a multiple of 16, >= mg_rainbow_packed_bytes()
+ *   scratch   members * mg_rainbow_learn_scratch_bytes(batch) bytes, 16-byte aligned
+ *
+ * Contract: for every member m, its learner block, loss, rows, proj, grads and packed net are bit for bit what
+ * mg_rainbow_learn gives on that member's buffers, counters, hyperparameters and slice of the noise. K updates
+ * in one call equal K calls. The launch order of a call is the lone learner's: the effective weights of the
+ * stored noise, the updates, one pack of all members -- so num_updates == 0 launches the first and the last and
+ * leaves packed_out current. On success the two learn calls advance every member's first_update and first_draw
+ * by num_updates; a refused call changes nothing. mg_host_rainbow_learn_many is the loop over the members of
+ * mg_host_rainbow_learn's update on HOST pointers, synchronously; it needs no table.
+ * mg_rainbow_sync_target_many: update_target (ranbowdqn.py:551-552) -- target := current, parameters and noise
+ * block -- for every member whose bit of `mask` is set, in one launch; a bit at or above `members` is refused.
+ * Refused before anything is read or launched, in mg_rainbow_learn's order: members outside 1 .. 64; a NULL
+ * learners, member or scratch, a member's NULL rows or counter; batch outside 1 .. 1024, capacity outside
+ * 1 .. 2^32, num_updates < 0; num_updates > 0 with noise NULL; a member's betas outside [0, 1); learners, scratch
+ * or packed_out not 16-byte, noise or an optional output not 4-byte aligned, packed_stride no multiple of 16; a
+ * member's rows or counter not 8-byte aligned; packed_stride or scratch too small; (device) table NULL, not
+ * 16-byte aligned or too small. A refusal of one member's fields names the member. */
+size_t mg_rainbow_learn_many_table_bytes(int32_t members); /* 0 outside 1 .. 64 */
+int mg_rainbow_learn_many_init(void* table, size_t table_bytes, const mg_dqn_member* member, int32_t members,
+                               void* stream);
+int mg_rainbow_learn_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member,
+                          int32_t members, int64_t capacity, int32_t batch, int32_t num_updates, const float* noise,
+                          float* loss_out, float* rows_out, float* proj_out, float* grads_out, void* packed_out,
+                          size_t packed_stride, void* scratch, size_t scratch_bytes, void* stream);
+int mg_host_rainbow_learn_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                               int32_t batch, int32_t num_updates, const float* noise, float* loss_out,
+                               float* rows_out, float* proj_out, float* grads_out, void* scratch,
+                               size_t scratch_bytes);
+int mg_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first_update, int32_t members,
+                          int32_t num_updates, float* noise_out, void* stream);
+int mg_host_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first_update, int32_t members,
+                               int32_t num_updates, float* noise_out);
+int mg_rainbow_sync_target_many(float* learners, int32_t members, uint64_t mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

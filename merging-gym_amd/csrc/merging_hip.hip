@@ -664,6 +664,55 @@ int mg_host_rainbow_learn(float* learner, const float* rows, const uint64_t* cou
   return rainbow_learn_host(C);
 }
 
+// ---- a population of Rainbow learners in mg_rainbow_learn's launches -------------------------------
+size_t mg_rainbow_learn_many_table_bytes(int32_t members) {
+  return members_ok(members) ? sizeof(LearnMember) * static_cast<size_t>(members) : 0;
+}
+
+int mg_rainbow_learn_many_init(void* table, size_t table_bytes, const mg_dqn_member* member, int32_t members,
+                               void* stream) {
+  const char* what = "mg_rainbow_learn_many_init";
+  if (!members_ok(members)) return fail(hipErrorInvalidValue, "%s: need 1 <= members <= 64", what);
+  if (!member) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (int e = check_rainbow_members_null(what, member, members)) return e;
+  if (int e = check_rainbow_members_betas(what, member, members)) return e;
+  if (int e = check_rainbow_members_aligned(what, member, members)) return e;
+  if (int e = check_rainbow_member_table(what, table, table_bytes, members)) return e;
+  for (int m = 0; m < members; ++m)  // by value, on the stream: nothing is copied from the caller's memory later
+    hipLaunchKernelGGL(learn_many_entry_kernel, dim3(1), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       static_cast<LearnMember*>(table) + m, learn_member_entry(member[m]));
+  return finish_launch(what);
+}
+
+int mg_rainbow_learn_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member,
+                          int32_t members, int64_t capacity, int32_t batch, int32_t num_updates, const float* noise,
+                          float* loss_out, float* rows_out, float* proj_out, float* grads_out, void* packed_out,
+                          size_t packed_stride, void* scratch, size_t scratch_bytes, void* stream) {
+  const RLearnManyCall C{learners, table, table_bytes, member, members, capacity, batch, num_updates, noise,
+                         loss_out, rows_out, proj_out, grads_out, packed_out, packed_stride, scratch, scratch_bytes,
+                         false};
+  if (int e = check_rainbow_learn_many("mg_rainbow_learn_many", C)) return e;
+  return rainbow_learn_many_device("mg_rainbow_learn_many", C, static_cast<hipStream_t>(stream));
+}
+
+int mg_host_rainbow_learn_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                               int32_t batch, int32_t num_updates, const float* noise, float* loss_out,
+                               float* rows_out, float* proj_out, float* grads_out, void* scratch,
+                               size_t scratch_bytes) {
+  const RLearnManyCall C{learners, nullptr, 0, member, members, capacity, batch, num_updates, noise,
+                         loss_out, rows_out, proj_out, grads_out, nullptr, 0, scratch, scratch_bytes, true};
+  if (int e = check_rainbow_learn_many("mg_host_rainbow_learn_many", C)) return e;
+  return rainbow_learn_many_host(C);
+}
+
+int mg_rainbow_sync_target_many(float* learners, int32_t members, uint64_t mask, void* stream) {
+  if (int e = check_rainbow_sync_many("mg_rainbow_sync_target_many", learners, members, mask)) return e;
+  if (mask == 0) return 0;
+  hipLaunchKernelGGL(rl_sync_many_kernel, dim3(grid_blocks(kRlParams + kRlEps), static_cast<unsigned>(members)),
+                     dim3(kBlock), 0, static_cast<hipStream_t>(stream), learners, mask);
+  return finish_launch("mg_rainbow_sync_target_many");
+}
+
 int mg_host_rainbow_project(const float* next_dist, const float* reward, const float* done, const float* support,
                             double gamma, float* proj, int64_t n) {
   if (n < 0) return fail(hipErrorInvalidValue, "%s", "n < 0");
@@ -834,6 +883,27 @@ int mg_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_upd
 int mg_host_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* noise_out) {
   if (int e = check_rainbow_noise("mg_host_rainbow_noise", num_updates, noise_out)) return e;
   host_rainbow_noise(noise_seed, first_update, num_updates, noise_out);
+  g_err[0] = '\0';
+  return 0;
+}
+
+int mg_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first_update, int32_t members,
+                          int32_t num_updates, float* noise_out, void* stream) {
+  if (int e = check_rainbow_noise_many("mg_rainbow_noise_many", noise_seed, first_update, members, num_updates,
+                                       noise_out))
+    return e;
+  if (num_updates == 0) return 0;
+  launch_rainbow_noise_many(make_rainbow_noise_many(noise_seed, first_update, members), num_updates, noise_out,
+                            static_cast<hipStream_t>(stream));
+  return finish_launch("mg_rainbow_noise_many");
+}
+
+int mg_host_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first_update, int32_t members,
+                               int32_t num_updates, float* noise_out) {
+  if (int e = check_rainbow_noise_many("mg_host_rainbow_noise_many", noise_seed, first_update, members, num_updates,
+                                       noise_out))
+    return e;
+  host_rainbow_noise_many(make_rainbow_noise_many(noise_seed, first_update, members), num_updates, noise_out);
   g_err[0] = '\0';
   return 0;
 }

@@ -71,8 +71,7 @@ struct RbTensors {
 };
 
 // One thread per packed 4-byte word: two bf16 weights of a fragment, or one fp32 bias / support value.
-__global__ void rainbow_pack_kernel(const RbTensors T, uint8_t* packed) {
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ inline void rainbow_pack_at(int w, const RbTensors& T, uint8_t* packed) {
   if (w >= kRbNetBytes / 4) return;
   const int off = 4 * w;
   // part p (0 hi, 1 mid, 2 lo) of the three-way bf16 split of b (hi + mid + lo == b)
@@ -142,6 +141,10 @@ __global__ void rainbow_pack_kernel(const RbTensors T, uint8_t* packed) {
   } else {
     *reinterpret_cast<float*>(packed + off) = v[0];
   }
+}
+
+__global__ void rainbow_pack_kernel(const RbTensors T, uint8_t* packed) {
+  rainbow_pack_at(blockIdx.x * blockDim.x + threadIdx.x, T, packed);
 }
 
 // ---------------------------------------------------------------------------- the head, host and device

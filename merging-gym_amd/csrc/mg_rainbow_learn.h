@@ -2,13 +2,16 @@
 // projection, the noisy-net forward and backward, Adam and the noise reset, with the per-element functions
 // the host twins (mg_host_rainbow_learn*) run too. The learner in both forms: the plain one is the prioritized
 // one (mg_per.h's tree, sample and update) without a tree, so a call has one check, one launch order beside
-// its host twin and one pair of drivers; the replay stores likewise.
+// its host twin and one pair of drivers; the replay stores likewise. A population of up to 64 plain learners
+// (mg_rainbow_learn_many) runs the same kernel bodies with the member in the grid: each kernel is a template on
+// its argument, RLearn for the lone call or RLearnMany, from which rl_member rebases member m's RLearn.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
 #include "mg_common.h"
 #include "mg_env.h"
 #include "mg_launch.h"
+#include "mg_learn.h"
 #include "mg_learn_core.h"
 #include "mg_per.h"
 #include "mg_rainbow.h"
@@ -383,11 +386,84 @@ inline void host_rl_forward_row(const RLearn& L, uint64_t live, int b) {
   }
 }
 
+// ---------------------------------------------------------------------------- the members of a call
+// A population (mg_rainbow_learn_many): up to 64 learners of one batch size and capacity in the lone learner's
+// launches, the member in the grid's y. What a member keeps for all its updates -- ring, counter, seed, gamma,
+// Adam's constants, rounded as learn_adam_scalars rounds them -- is mg_learn.h's LearnMember in a device table
+// (mg_rainbow_learn_many_init); the per-update values -- each member's draw, Adam's step and bc2s from the
+// host's doubles -- travel by value. The table is a typed global pointer of the kernel argument, so an entry
+// arrives by scalar loads.
+struct RLearnMany {
+  float* learners;           // [members, kRlLearner]
+  float* scratch;            // [members, stride]
+  const LearnMember* table;  // [members]
+  const float* noise;        // this update's factors [members][2][kRlFactors]
+  float *rows_out, *loss_out, *proj_out, *grads_out;  // this update's [members, ...], or NULL
+  int64_t stride;            // floats of one member's scratch: rl_scratch(B, false).total
+  int64_t cap;
+  int32_t B, members;
+  float inv_b;
+  uint64_t draw[kMaxMembers];
+  float step[kMaxMembers];
+  float bc2s[kMaxMembers];
+};
+static_assert(sizeof(RLearnMany) <= 1200, "the by-value kernel argument stays well inside HIP's 4096 bytes");
+
+// the scratch sections of a learner whose scratch starts at s
+MG_HD void rl_set_scratch(RLearn& L, float* s, const RlScratch& S) {
+  L.rows = s + S.rows, L.h1 = s + S.h1, L.h2 = s + S.h2, L.hv = s + S.hv, L.ha = s + S.ha, L.dlog = s + S.dlog;
+  L.dhv = s + S.dhv, L.dha = s + S.dha, L.dh2 = s + S.dh2, L.dh1 = s + S.dh1, L.lossb = s + S.lossb;
+  L.g = s + S.g, L.geff = s + S.geff, L.eff = s + S.eff;
+}
+
+// Member m's RLearn: its block, its scratch, its rows of the outputs and the noise, its entry and per-update
+// scalars. The lone call's argument is its one member's already.
+MG_HD RLearn rl_member(const RLearnMany& Q, int m) {
+  const LearnMember& T = Q.table[m];
+  RLearn L{};
+  L.buf = Q.learners + static_cast<int64_t>(m) * kRlLearner;
+  L.ring = T.ring, L.counter = T.counter, L.cap = Q.cap, L.seed = T.seed, L.draw = Q.draw[m], L.B = Q.B;
+  rl_set_scratch(L, Q.scratch + m * Q.stride, rl_scratch(Q.B, false));
+  L.noise = Q.noise ? Q.noise + static_cast<int64_t>(m) * 2 * kRlFactors : nullptr;  // NULL in front of the updates
+  L.rows_out = Q.rows_out ? Q.rows_out + static_cast<int64_t>(m) * Q.B * kRlRow : nullptr;
+  L.loss_out = Q.loss_out ? Q.loss_out + m : nullptr;
+  L.proj_out = Q.proj_out ? Q.proj_out + static_cast<int64_t>(m) * Q.B * kRbAtoms : nullptr;
+  L.grads_out = Q.grads_out ? Q.grads_out + static_cast<int64_t>(m) * kRlParams : nullptr;
+  L.gamma = T.gamma, L.inv_b = Q.inv_b;
+  L.A = LearnAdam{T.b1, T.omb1, T.b2, T.omb2, Q.step[m], Q.bc2s[m], T.eps};
+  return L;
+}
+MG_HD const RLearn& rl_member(const RLearn& L, int) { return L; }
+
+// What the two noisy backward launches read: the lone call's layers as the host built them, or member m's
+// built where they are used.
+struct RlHeads {
+  LearnBwd G0, G1;
+};
+struct RlStreams {
+  RLearn L;
+  LearnBwd Gv, Ga;
+};
+MG_HD const RlHeads& rl_heads(const RlHeads& H, int) { return H; }
+MG_HD const RlStreams& rl_streams(const RlStreams& S, int) { return S; }
+MG_HD RlHeads rl_heads(const RLearnMany& Q, int m) {
+  const RLearn L = rl_member(Q, m);
+  return RlHeads{rl_bwd_layer(L, 0), rl_bwd_layer(L, 1)};
+}
+MG_HD RlStreams rl_streams(const RLearnMany& Q, int m) {
+  const RLearn L = rl_member(Q, m);
+  return RlStreams{L, rl_bwd_layer(L, 2), rl_bwd_layer(L, 3)};
+}
+
 // ---------------------------------------------------------------------------- kernels
+// One body each for the lone learner (Arg = RLearn, RlHeads, RlStreams: blockIdx.y is 0 and unused) and the
+// population (Arg = RLearnMany: blockIdx.y is the member).
 // One block per minibatch row: host_rl_forward_row's steps, the activations in LDS, one thread per unit. The two
 // forwards run side by side -- threads 0..319 the target's on s' (pass 1), 320..639 the current's on s (pass 0) --
 // through the same phases; only the loss waits for the projection.
-__global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const RLearn L) {
+template <class Arg>
+__global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const Arg Q) {
+  const RLearn& L = rl_member(Q, blockIdx.y);
   __shared__ float srow[kRlRow], h1[2][kRbH1], h2[2][kRbH2], hv[2][kRbHS], ha[2][kRbHS], lg[2][kRbLogits];
   __shared__ float p[2][kRbActions * kRbAtoms], q[2][kRbActions], bb[kRbAtoms], proj[kRbAtoms], dx[kRbAtoms];
   const int b = blockIdx.x;
@@ -452,7 +528,10 @@ __global__ __launch_bounds__(2 * kRlThreads) void rl_forward_kernel(const RLearn
 }
 
 // two layers' items in one launch
-__global__ __launch_bounds__(kBlock) void rl_bwd_heads_kernel(const LearnBwd G0, const LearnBwd G1) {
+template <class Arg>
+__global__ __launch_bounds__(kBlock) void rl_bwd_heads_kernel(const Arg Q) {
+  const RlHeads& H = rl_heads(Q, blockIdx.y);
+  const LearnBwd &G0 = H.G0, &G1 = H.G1;
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const int64_t n0 = learn_bwd_items(G0);
   if (idx < n0)
@@ -462,7 +541,11 @@ __global__ __launch_bounds__(kBlock) void rl_bwd_heads_kernel(const LearnBwd G0,
 }
 
 // the hidden streams' gradients and, behind them, the B x 64 items of rl_dh2_at
-__global__ __launch_bounds__(kBlock) void rl_bwd_streams_kernel(const RLearn L, const LearnBwd Gv, const LearnBwd Ga) {
+template <class Arg>
+__global__ __launch_bounds__(kBlock) void rl_bwd_streams_kernel(const Arg Q) {
+  const RlStreams& S = rl_streams(Q, blockIdx.y);
+  const RLearn& L = S.L;
+  const LearnBwd &Gv = S.Gv, &Ga = S.Ga;
   int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const int64_t nv = learn_bwd_items(Gv), na = learn_bwd_items(Ga);
   if (idx < nv) return learn_bwd_at(Gv, idx);
@@ -471,18 +554,41 @@ __global__ __launch_bounds__(kBlock) void rl_bwd_streams_kernel(const RLearn L, 
   idx -= na;
   if (idx < static_cast<int64_t>(L.B) * kRbH2) rl_dh2_at(L, idx);
 }
-MG_HD int64_t rl_bwd_streams_items(const RLearn& L, const LearnBwd& Gv, const LearnBwd& Ga) {
-  return learn_bwd_items(Gv) + learn_bwd_items(Ga) + static_cast<int64_t>(L.B) * kRbH2;
+MG_HD int64_t rl_bwd_heads_items(const RlHeads& H) { return learn_bwd_items(H.G0) + learn_bwd_items(H.G1); }
+MG_HD int64_t rl_bwd_streams_items(const RlStreams& S) {
+  return learn_bwd_items(S.Gv) + learn_bwd_items(S.Ga) + static_cast<int64_t>(S.L.B) * kRbH2;
 }
 
-__global__ __launch_bounds__(kBlock) void rl_adam_kernel(const RLearn L) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i <= kRlParams) rl_adam_at(L, i);
+// learn_bwd_kernel (mg_learn_core.h, the DQN learner's too) for a member's plain layer WHICH (4 linear2, 5 linear1)
+template <int WHICH>
+__global__ __launch_bounds__(kBlock) void rl_bwd_plain_many_kernel(const RLearnMany Q) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const LearnBwd G = rl_bwd_layer(rl_member(Q, blockIdx.y), WHICH);
+  if (idx < learn_bwd_items(G)) learn_bwd_at(G, idx);
 }
 
-__global__ __launch_bounds__(kBlock) void rl_noise_eff_kernel(const RLearn L, int redraw) {
+template <class Arg>
+__global__ __launch_bounds__(kBlock) void rl_adam_kernel(const Arg Q) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < 2 * kRlEps) rl_noise_eff_at(L, i, redraw != 0);
+  if (i <= kRlParams) rl_adam_at(rl_member(Q, blockIdx.y), i);
+}
+
+template <class Arg>
+__global__ __launch_bounds__(kBlock) void rl_noise_eff_kernel(const Arg Q, int redraw) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < 2 * kRlEps) rl_noise_eff_at(rl_member(Q, blockIdx.y), i, redraw != 0);
+}
+
+// update_target (:551-552) for every member whose bit is set: target := current, the parameters and the noise
+// block.
+__global__ __launch_bounds__(kBlock) void rl_sync_many_kernel(float* learners, uint64_t mask) {
+  const int m = blockIdx.y, i = blockIdx.x * kBlock + threadIdx.x;
+  if (!((mask >> m) & 1)) return;
+  float* buf = learners + static_cast<int64_t>(m) * kRlLearner;
+  if (i < kRlParams)
+    buf[kRlParams + i] = buf[i];
+  else if (i < kRlParams + kRlEps)
+    buf[kRlOffEps + kRlEps + (i - kRlParams)] = buf[kRlOffEps + (i - kRlParams)];
 }
 
 // ---------------------------------------------------------------------------- host side of a call
@@ -588,9 +694,7 @@ void make_rainbow_learn(RLearnCall& C) {
   RLearn& L = C.L;
   L.buf = C.learner;
   L.ring = C.rows, L.counter = C.counter, L.cap = C.capacity, L.seed = C.seed, L.B = C.batch;
-  L.rows = s + S.rows, L.h1 = s + S.h1, L.h2 = s + S.h2, L.hv = s + S.hv, L.ha = s + S.ha, L.dlog = s + S.dlog;
-  L.dhv = s + S.dhv, L.dha = s + S.dha, L.dh2 = s + S.dh2, L.dh1 = s + S.dh1, L.lossb = s + S.lossb;
-  L.g = s + S.g, L.geff = s + S.geff, L.eff = s + S.eff;
+  rl_set_scratch(L, s, S);
   L.gamma = static_cast<float>(C.hyper->gamma);
   L.inv_b = static_cast<float>(1.0 / C.batch);
   if (!C.prioritized) return;
@@ -625,26 +729,24 @@ void rainbow_learn_set_update(RLearnCall& C, int32_t u) {
 void launch_rainbow_learn_update(const RLearnCall& C, hipStream_t st) {
   const RLearn& L = C.L;
   if (C.prioritized) hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(L.B)), dim3(kBlock), 0, st, C.P);
-  hipLaunchKernelGGL(rl_forward_kernel, dim3(L.B), dim3(2 * kRlThreads), 0, st, L);
-  const LearnBwd G0 = rl_bwd_layer(L, 0), G1 = rl_bwd_layer(L, 1), G2 = rl_bwd_layer(L, 2), G3 = rl_bwd_layer(L, 3);
-  hipLaunchKernelGGL(rl_bwd_heads_kernel, dim3(grid_blocks(learn_bwd_items(G0) + learn_bwd_items(G1))), dim3(kBlock),
-                     0, st, G0, G1);
-  hipLaunchKernelGGL(rl_bwd_streams_kernel, dim3(grid_blocks(rl_bwd_streams_items(L, G2, G3))), dim3(kBlock), 0, st, L,
-                     G2, G3);
+  hipLaunchKernelGGL(rl_forward_kernel<RLearn>, dim3(L.B), dim3(2 * kRlThreads), 0, st, L);
+  const RlHeads H{rl_bwd_layer(L, 0), rl_bwd_layer(L, 1)};
+  const RlStreams S{L, rl_bwd_layer(L, 2), rl_bwd_layer(L, 3)};
+  hipLaunchKernelGGL(rl_bwd_heads_kernel<RlHeads>, dim3(grid_blocks(rl_bwd_heads_items(H))), dim3(kBlock), 0, st, H);
+  hipLaunchKernelGGL(rl_bwd_streams_kernel<RlStreams>, dim3(grid_blocks(rl_bwd_streams_items(S))), dim3(kBlock), 0, st,
+                     S);
   for (int which = 4; which < 6; ++which) {
     const LearnBwd G = rl_bwd_layer(L, which);
     hipLaunchKernelGGL(learn_bwd_kernel, dim3(grid_blocks(learn_bwd_items(G))), dim3(kBlock), 0, st, G);
   }
-  hipLaunchKernelGGL(rl_adam_kernel, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
-  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 1);
+  hipLaunchKernelGGL(rl_adam_kernel<RLearn>, dim3(grid_blocks(kRlParams + 1)), dim3(kBlock), 0, st, L);
+  hipLaunchKernelGGL(rl_noise_eff_kernel<RLearn>, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, L, 1);
   if (C.prioritized) hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(kPerTail), 0, st, C.U);
 }
 
-// One update on the host: the kernels' per-item functions in the kernels' order.
-void host_rainbow_learn_update(const RLearnCall& C) {
-  const RLearn& L = C.L;
-  if (C.prioritized)
-    for (int b = 0; b < L.B; ++b) per_sample_at(C.P, b);
+// One update on the host: the kernels' per-item functions in the kernels' order. First the seven launches'
+// loops on one learner (a member's too), then the update around them.
+void host_rl_update(const RLearn& L) {
   const uint64_t live = learn_rows_live(L.cap, L.counter, 1);
   for (int b = 0; b < L.B; ++b) host_rl_forward_row(L, live, b);
   for (int which = 0; which < 6; ++which) {
@@ -655,11 +757,16 @@ void host_rainbow_learn_update(const RLearnCall& C) {
   }
   for (int i = 0; i <= kRlParams; ++i) rl_adam_at(L, i);
   for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, true);
+}
+void host_rainbow_learn_update(const RLearnCall& C) {
+  if (C.prioritized)
+    for (int b = 0; b < C.L.B; ++b) per_sample_at(C.P, b);
+  host_rl_update(C.L);
   if (C.prioritized) host_per_update(C.U);
 }
 
 // What rainbow_pack_kernel packs for acting: the current model's plain layers, effective weights e = L.eff, support.
-RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
+MG_HD RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
   const RlNoisy V1 = rl_noisy(0), V2 = rl_noisy(1), A1 = rl_noisy(2), A2 = rl_noisy(3);
   return RbTensors{learner + kRlW1, learner + kRlB1, learner + kRlW2, learner + kRlB2,
                    e + V1.e, e + V1.e + V1.out * kRbHS, e + V2.e, e + V2.e + V2.out * kRbHS,
@@ -672,7 +779,7 @@ RbTensors rainbow_learn_tensors(const float* learner, const float* e) {
 // of the current model's effective weights.
 int rainbow_learn_device(const char* what, RLearnCall& C, hipStream_t st) {
   make_rainbow_learn(C);
-  hipLaunchKernelGGL(rl_noise_eff_kernel, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, C.L, 0);
+  hipLaunchKernelGGL(rl_noise_eff_kernel<RLearn>, dim3(grid_blocks(2 * kRlEps)), dim3(kBlock), 0, st, C.L, 0);
   for (int32_t u = 0; u < C.num_updates; ++u) {
     rainbow_learn_set_update(C, u);
     launch_rainbow_learn_update(C, st);
@@ -692,6 +799,187 @@ int rainbow_learn_host(RLearnCall& C) {
     host_rainbow_learn_update(C);
   }
   g_err[0] = '\0';
+  return 0;
+}
+
+// ============================================================================ a population of learners
+// rainbow_pack_kernel with blockIdx.y the member: its current model's plain layers, effective weights and support
+// into its row of the packed buffer.
+__global__ void rainbow_pack_many_kernel(const float* learners, const float* scratch, int64_t stride, int64_t eff,
+                                         uint8_t* packed, int64_t packed_stride) {
+  const int64_t m = blockIdx.y;
+  rainbow_pack_at(blockIdx.x * blockDim.x + threadIdx.x,
+                  rainbow_learn_tensors(learners + m * kRlLearner, scratch + m * stride + eff),
+                  packed + m * packed_stride);
+}
+
+// What the population's entry points refuse of the member list, in check_rainbow_learn's three steps: the
+// pointers, Adam's betas, the alignment (hyper.target_period is not read).
+int check_rainbow_members_null(const char* what, const mg_dqn_member* member, int32_t members) {
+  for (int m = 0; m < members; ++m)
+    if (!member[m].rows || !member[m].counter) return fail_member(what, m, "NULL pointer (rows or counter)");
+  return 0;
+}
+int check_rainbow_members_betas(const char* what, const mg_dqn_member* member, int32_t members) {
+  for (int m = 0; m < members; ++m) {
+    const mg_dqn_hyper& H = member[m].hyper;
+    if (!(H.beta1 >= 0.0 && H.beta1 < 1.0 && H.beta2 >= 0.0 && H.beta2 < 1.0))
+      return fail_member(what, m, "need 0 <= beta1 < 1 and 0 <= beta2 < 1");
+  }
+  return 0;
+}
+int check_rainbow_members_aligned(const char* what, const mg_dqn_member* member, int32_t members) {
+  for (int m = 0; m < members; ++m)
+    if (misaligned(member[m].rows, 7) || misaligned(member[m].counter, 7))
+      return fail_member(what, m, "rows and counter must be 8-byte aligned");
+  return 0;
+}
+
+int check_rainbow_member_table(const char* what, const void* table, size_t table_bytes, int32_t members) {
+  if (!table) return fail(hipErrorInvalidValue, "%s: table is NULL", what);
+  if (misaligned(table, 15)) return fail(hipErrorInvalidValue, "%s: table must be 16-byte aligned", what);
+  if (table_bytes < sizeof(LearnMember) * static_cast<size_t>(members))
+    return fail(hipErrorInvalidValue, "%s: table smaller than mg_rainbow_learn_many_table_bytes(members)", what);
+  return 0;
+}
+
+// One call of mg_rainbow_learn_many or its host twin, as the entry point took it (table and packed_out NULL on
+// the host).
+struct RLearnManyCall {
+  float* learners;
+  const void* table;
+  size_t table_bytes;
+  mg_dqn_member* member;
+  int32_t members;
+  int64_t capacity;
+  int32_t batch, num_updates;
+  const float* noise;
+  float *loss_out, *rows_out, *proj_out, *grads_out;
+  void* packed_out;
+  size_t packed_stride;
+  void* scratch;
+  size_t scratch_bytes;
+  bool host;
+};
+
+// What the two refuse, before anything is read or launched: check_rainbow_learn's checks in its order, the
+// members' behind the call's at each step.
+int check_rainbow_learn_many(const char* what, const RLearnManyCall& C) {
+  if (!members_ok(C.members)) return fail(hipErrorInvalidValue, "%s: need 1 <= members <= 64", what);
+  if (!C.learners || !C.member || !C.scratch) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (int e = check_rainbow_members_null(what, C.member, C.members)) return e;
+  if (int e = check_learn_sizes(what, C.batch, C.capacity, C.num_updates)) return e;
+  if (C.num_updates > 0 && !C.noise)
+    return fail(hipErrorInvalidValue, "%s: noise is NULL (num_updates x members x 2 x 1124 factors)", what);
+  if (int e = check_rainbow_members_betas(what, C.member, C.members)) return e;
+  if (misaligned(C.learners, 15) || misaligned(C.scratch, 15) || misaligned(C.packed_out, 15) ||
+      misaligned(C.noise, 3) || misaligned(C.loss_out, 3) || misaligned(C.rows_out, 3) || misaligned(C.proj_out, 3) ||
+      misaligned(C.grads_out, 3) || (C.packed_out && C.packed_stride % 16 != 0))
+    return fail(hipErrorInvalidValue,
+                "%s: learners, scratch and packed_out must be 16-byte, noise and the optional outputs 4-byte "
+                "aligned, packed_stride a multiple of 16", what);
+  if (int e = check_rainbow_members_aligned(what, C.member, C.members)) return e;
+  if (C.packed_out && C.packed_stride < static_cast<size_t>(kRbNetBytes))
+    return fail(hipErrorInvalidValue, "%s: packed_stride smaller than mg_rainbow_packed_bytes()", what);
+  const size_t one = static_cast<size_t>(rl_scratch(C.batch, false).total) * sizeof(float);
+  if (C.scratch_bytes < one * static_cast<size_t>(C.members))
+    return fail(hipErrorInvalidValue, "%s: scratch smaller than members * mg_rainbow_learn_scratch_bytes(batch)", what);
+  if (C.host) return 0;
+  return check_rainbow_member_table(what, C.table, C.table_bytes, C.members);
+}
+
+// The fields of RLearnMany that do not change from one update of a call to the next.
+RLearnMany make_rainbow_learn_many(const RLearnManyCall& C, const LearnMember* table) {
+  RLearnMany Q{};
+  Q.learners = C.learners, Q.scratch = static_cast<float*>(C.scratch), Q.table = table;
+  Q.stride = rl_scratch(C.batch, false).total;
+  Q.cap = C.capacity, Q.B = C.batch, Q.members = C.members;
+  Q.inv_b = static_cast<float>(1.0 / C.batch);
+  return Q;
+}
+
+// Update number u of a call: every member's draw and Adam's step t + 1 (t = its first_update + u) from the
+// host's doubles, and the update's rows of the noise and the outputs.
+void rainbow_learn_many_set_update(RLearnMany& Q, const RLearnManyCall& C, int32_t u) {
+  for (int m = 0; m < Q.members; ++m) {
+    const LearnAdam A = learn_adam_scalars(&C.member[m].hyper, C.member[m].first_update + static_cast<uint64_t>(u));
+    Q.step[m] = A.step, Q.bc2s[m] = A.bc2s;
+    Q.draw[m] = C.member[m].first_draw + static_cast<uint64_t>(u);
+  }
+  const int64_t um = static_cast<int64_t>(u) * Q.members;
+  Q.noise = C.noise + um * 2 * kRlFactors;
+  Q.loss_out = C.loss_out ? C.loss_out + um : nullptr;
+  Q.rows_out = C.rows_out ? C.rows_out + um * Q.B * kRlRow : nullptr;
+  Q.proj_out = C.proj_out ? C.proj_out + um * Q.B * kRbAtoms : nullptr;
+  Q.grads_out = C.grads_out ? C.grads_out + um * kRlParams : nullptr;
+}
+
+// One update of all members on the device: launch_rainbow_learn_update's seven launches, the member in the
+// grid's y. The grids depend on the batch size alone.
+void launch_rainbow_learn_many_update(const RLearnMany& Q, hipStream_t st) {
+  const unsigned M = static_cast<unsigned>(Q.members);
+  RLearn shape{};
+  shape.B = Q.B;
+  rl_set_scratch(shape, Q.scratch, rl_scratch(Q.B, false));
+  const RlHeads H{rl_bwd_layer(shape, 0), rl_bwd_layer(shape, 1)};
+  const RlStreams S{shape, rl_bwd_layer(shape, 2), rl_bwd_layer(shape, 3)};
+  const auto plain = [&](int which) { return dim3(grid_blocks(learn_bwd_items(rl_bwd_layer(shape, which))), M); };
+  hipLaunchKernelGGL(rl_forward_kernel<RLearnMany>, dim3(Q.B, M), dim3(2 * kRlThreads), 0, st, Q);
+  hipLaunchKernelGGL(rl_bwd_heads_kernel<RLearnMany>, dim3(grid_blocks(rl_bwd_heads_items(H)), M), dim3(kBlock), 0, st,
+                     Q);
+  hipLaunchKernelGGL(rl_bwd_streams_kernel<RLearnMany>, dim3(grid_blocks(rl_bwd_streams_items(S)), M), dim3(kBlock), 0,
+                     st, Q);
+  hipLaunchKernelGGL(rl_bwd_plain_many_kernel<4>, plain(4), dim3(kBlock), 0, st, Q);
+  hipLaunchKernelGGL(rl_bwd_plain_many_kernel<5>, plain(5), dim3(kBlock), 0, st, Q);
+  hipLaunchKernelGGL(rl_adam_kernel<RLearnMany>, dim3(grid_blocks(kRlParams + 1), M), dim3(kBlock), 0, st, Q);
+  hipLaunchKernelGGL(rl_noise_eff_kernel<RLearnMany>, dim3(grid_blocks(2 * kRlEps), M), dim3(kBlock), 0, st, Q, 1);
+}
+
+// mg_rainbow_learn_many after its check: rainbow_learn_device's order for all members at once -- the effective
+// weights of the stored noise, the updates, the pack -- so num_updates == 0 still packs.
+int rainbow_learn_many_device(const char* what, const RLearnManyCall& C, hipStream_t st) {
+  RLearnMany Q = make_rainbow_learn_many(C, static_cast<const LearnMember*>(C.table));
+  const unsigned M = static_cast<unsigned>(Q.members);
+  hipLaunchKernelGGL(rl_noise_eff_kernel<RLearnMany>, dim3(grid_blocks(2 * kRlEps), M), dim3(kBlock), 0, st, Q, 0);
+  for (int32_t u = 0; u < C.num_updates; ++u) {
+    rainbow_learn_many_set_update(Q, C, u);
+    launch_rainbow_learn_many_update(Q, st);
+  }
+  if (C.packed_out)
+    hipLaunchKernelGGL(rainbow_pack_many_kernel, dim3(grid_blocks(kRbNetBytes / 4), M), dim3(kBlock), 0, st, Q.learners,
+                       Q.scratch, Q.stride, rl_scratch(Q.B, false).eff, static_cast<uint8_t*>(C.packed_out),
+                       static_cast<int64_t>(C.packed_stride));
+  if (int e = finish_launch(what)) return e;
+  learn_advance(C.member, C.members, C.num_updates);
+  return 0;
+}
+
+// mg_host_rainbow_learn_many after its check: host_rl_update member by member, each on the RLearn the kernels
+// rebase, from a table on the stack.
+int rainbow_learn_many_host(const RLearnManyCall& C) {
+  LearnMember table[kMaxMembers];
+  for (int m = 0; m < C.members; ++m) table[m] = learn_member_entry(C.member[m]);
+  RLearnMany Q = make_rainbow_learn_many(C, table);
+  for (int m = 0; m < Q.members; ++m) {
+    const RLearn L = rl_member(Q, m);
+    for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
+  }
+  for (int32_t u = 0; u < C.num_updates; ++u) {
+    rainbow_learn_many_set_update(Q, C, u);
+    for (int m = 0; m < Q.members; ++m) host_rl_update(rl_member(Q, m));
+  }
+  learn_advance(C.member, C.members, C.num_updates);
+  g_err[0] = '\0';
+  return 0;
+}
+
+// mg_rainbow_sync_target_many's refusals.
+int check_rainbow_sync_many(const char* what, const float* learners, int32_t members, uint64_t mask) {
+  if (!members_ok(members)) return fail(hipErrorInvalidValue, "%s: need 1 <= members <= 64", what);
+  if (!learners) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (misaligned(learners, 15)) return fail(hipErrorInvalidValue, "%s: learners must be 16-byte aligned", what);
+  if (members < kMaxMembers && (mask >> members) != 0)
+    return fail(hipErrorInvalidValue, "%s: mask has a bit at or above members", what);
   return 0;
 }
 

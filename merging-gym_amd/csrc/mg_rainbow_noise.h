@@ -2,7 +2,8 @@
 // keyed by (noise_seed, update, model, factor) -- Philox words, a 52-bit uniform, the inverse normal CDF in fp64
 // (Wichura's AS 241, PPND16) and _scale_noise's sign(x) sqrt|x| -- with the per-element functions the host twin
 // (mg_host_rainbow_noise) runs too, so both fill the same [U][2][kRlFactors] bits. The contract is in
-// include/merging_hip.h at mg_rainbow_noise.
+// include/merging_hip.h at mg_rainbow_noise. A population's factors [U][M][2][kRlFactors] come from one launch
+// of the same functions (mg_rainbow_noise_many).
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -129,6 +130,58 @@ void launch_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t nu
 }
 void host_rainbow_noise(uint64_t noise_seed, uint64_t first_update, int32_t num_updates, float* out) {
   for (int64_t i = 0; i < rn_noise_items(num_updates); ++i) out[i] = rn_noise_at(noise_seed, first_update, i);
+}
+
+// ---------------------------------------------------------------------------- a population's factors
+// [U][M][2][kRlFactors] in one launch: element (u, m, model, f) = rn_factor_at(noise_seed[m], first_update[m] + u,
+// model, f), what mg_rainbow_noise gives member m. The members' keys travel in the kernel argument (64 x 16 B).
+// Each (u, m) takes kRnBlocks whole blocks, so a block's member is uniform and its key arrives by scalar loads.
+struct RnMany {
+  uint64_t noise_seed[kMaxMembers];
+  uint64_t first_update[kMaxMembers];
+  int32_t members;
+};
+static_assert(sizeof(RnMany) <= 1100, "the by-value kernel argument stays well inside HIP's 4096 bytes");
+constexpr int kRnBlocks = (2 * kRlFactors + kBlock - 1) / kBlock;
+
+MG_HD float rn_noise_many_at(const RnMany& R, int64_t um, int r) {
+  const int m = static_cast<int>(um % R.members);
+  return rn_factor_at(R.noise_seed[m], R.first_update[m] + static_cast<uint64_t>(um / R.members), r / kRlFactors,
+                      r % kRlFactors);
+}
+
+__global__ __launch_bounds__(kBlock) void rainbow_noise_many_kernel(const RnMany R, float* out) {
+  const int64_t um = blockIdx.x / kRnBlocks;
+  const int r = static_cast<int>(blockIdx.x % kRnBlocks) * kBlock + threadIdx.x;
+  if (r < 2 * kRlFactors) out[um * (2 * kRlFactors) + r] = rn_noise_many_at(R, um, r);
+}
+
+int check_rainbow_noise_many(const char* what, const uint64_t* noise_seed, const uint64_t* first_update,
+                             int32_t members, int32_t num_updates, const float* noise_out) {
+  if (!members_ok(members)) return fail(hipErrorInvalidValue, "%s: need 1 <= members <= 64", what);
+  if (!noise_seed || !first_update || !noise_out) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  if (num_updates < 0) return fail(hipErrorInvalidValue, "%s: num_updates < 0", what);
+  if (misaligned(noise_out, 3)) return fail(hipErrorInvalidValue, "%s: noise_out must be 4-byte aligned", what);
+  if (static_cast<int64_t>(num_updates) * members > static_cast<int64_t>(0x7fffffff) / kRnBlocks)
+    return fail(hipErrorInvalidValue, "%s: num_updates * members exceeds the grid limit", what);
+  return 0;
+}
+
+RnMany make_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first_update, int32_t members) {
+  RnMany R{};
+  for (int m = 0; m < members; ++m) R.noise_seed[m] = noise_seed[m], R.first_update[m] = first_update[m];
+  R.members = members;
+  return R;
+}
+void launch_rainbow_noise_many(const RnMany& R, int32_t num_updates, float* out, hipStream_t st) {
+  const int64_t um = static_cast<int64_t>(num_updates) * R.members;
+  if (um == 0) return;
+  hipLaunchKernelGGL(rainbow_noise_many_kernel, dim3(static_cast<unsigned>(um * kRnBlocks)), dim3(kBlock), 0, st, R,
+                     out);
+}
+void host_rainbow_noise_many(const RnMany& R, int32_t num_updates, float* out) {
+  for (int64_t um = 0; um < static_cast<int64_t>(num_updates) * R.members; ++um)
+    for (int r = 0; r < 2 * kRlFactors; ++r) out[um * (2 * kRlFactors) + r] = rn_noise_many_at(R, um, r);
 }
 
 void launch_rainbow_ndtri(const double* u, double* z, int64_t n, hipStream_t st) {

@@ -24,6 +24,10 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .population import DQNPopulation
 
         return DQNPopulation
+    if name == "RainbowPopulation":
+        from .rainbow_population import RainbowPopulation
+
+        return RainbowPopulation
     if name == "RainbowNet":
         from .rainbow import RainbowNet
 

@@ -267,6 +267,19 @@ def _load(path=LIB_PATH):
     lib.mg_host_rainbow_ndtri.argtypes = [_P, _P, _c.c_int64]
     for f in (lib.mg_rainbow_noise, lib.mg_host_rainbow_noise, lib.mg_rainbow_ndtri, lib.mg_host_rainbow_ndtri):
         f.restype = _c.c_int
+    # a population of Rainbow learners (additive to ABI 21): its table, learn, noise and target copy
+    lib.mg_rainbow_learn_many_table_bytes.argtypes = [_c.c_int32]
+    lib.mg_rainbow_learn_many_table_bytes.restype = _c.c_size_t
+    lib.mg_rainbow_learn_many_init.argtypes = [_P, _c.c_size_t, MP, _c.c_int32, _P]
+    rl_many = [MP, _c.c_int32, _c.c_int64, _c.c_int32, _c.c_int32, _P, _P, _P, _P, _P]
+    lib.mg_rainbow_learn_many.argtypes = [_P, _P, _c.c_size_t] + rl_many + [_P, _c.c_size_t, _P, _c.c_size_t, _P]
+    lib.mg_host_rainbow_learn_many.argtypes = [_P] + rl_many + [_P, _c.c_size_t]
+    lib.mg_rainbow_noise_many.argtypes = [_P, _P, _c.c_int32, _c.c_int32, _P, _P]
+    lib.mg_host_rainbow_noise_many.argtypes = [_P, _P, _c.c_int32, _c.c_int32, _P]
+    lib.mg_rainbow_sync_target_many.argtypes = [_P, _c.c_int32, _c.c_uint64, _P]
+    for f in (lib.mg_rainbow_learn_many_init, lib.mg_rainbow_learn_many, lib.mg_host_rainbow_learn_many,
+              lib.mg_rainbow_noise_many, lib.mg_host_rainbow_noise_many, lib.mg_rainbow_sync_target_many):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

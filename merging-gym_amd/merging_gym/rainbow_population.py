@@ -1,0 +1,264 @@
+"""RainbowPopulation: M independent RainbowLearners trained by one set of launches.
+
+Rainbow's users sweep seeds, lr, gamma and opponents as DQN's do, and one RainbowLearner.learn() is a dependent
+chain of seven small launches that leaves most of the device idle. A population runs M learners through the
+same seven launches (libmerging_hip.so's mg_rainbow_learn_many), each on its own nets, replay, minibatch seed,
+noise seed, counters and hyperparameters; the noise is always drawn on the device (mg_rainbow_noise_many, one
+launch for all members and updates of a call), so learn() does no host work and no upload:
+
+    replays = [RainbowReplay(10000, device="cuda:0") for _ in range(8)]
+    pop = RainbowPopulation([sd] * 8, replays, lr=[0.001, 0.0005, 0.002] + [0.001] * 5, seed=range(8))
+    envs = [MergeVecEnv(1024, device="cuda:0") for _ in range(8)]
+    for m, env in enumerate(envs):                          # acting is still one rollout and one store per member
+        obs0 = env.observe().clone()
+        replays[m].store_rollout(obs0, env.rollout_rainbow(16, pop.nets[m]))
+    pop.learn(4)                                            # four updates of all eight
+    pop.sync_target([0, 3])                                 # update_target for members 0 and 3, one launch
+    pop.copy_member(best, worst)                            # population-based training's exploit step
+
+Member m is bit for bit the lone RainbowLearner(net, replay, ..., generator=DeviceNoise(noise_seed[m])) built from
+the same net, replay, seeds and hyperparameters: member_state_dict(m) is that learner's state_dict() and loads into
+one, and back. Fused acting for all members (a many-member rollout_rainbow and replay store) is not part of this
+class yet: members act through M rollout_rainbow calls on pop.nets[m], as above.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+from . import _native
+from ._base import MAX_MEMBERS, per_member
+from ._device import U64, cuda_device, ptr, raw_stream, require_gpu
+from .rainbow import NUM_ATOMS, RainbowNet
+from .rainbow_learn import (LEARNER_FLOATS, NUM_FACTORS, NUM_PARAMS, ROW, PrioritizedRainbowReplay, RainbowReplay,
+                            _LearnerNet, learner_array, model_state_dict)
+
+
+class _Member:
+    """What a _LearnerNet asks of its learner, for member m of a population."""
+
+    def __init__(self, pop, m):
+        self._pop, self._m = pop, m
+
+    @property
+    def _packed(self):
+        return self._pop._packed[self._m]
+
+    def current_state_dict(self):
+        return self._pop.current_state_dict(self._m)
+
+
+class RainbowPopulation:
+    def __init__(self, nets, replays, lr=0.001, gamma=0.99, batch_size: int = 32, seed=0, noise_seed=None,
+                 betas=(0.9, 0.999), eps=1e-8, device=None):
+        """nets: M RainbowNets or RainbowDQN.state_dict()s; every member's current and target model both start
+        from its net, noise included. replays: M RainbowReplays of one capacity on one device; the same replay may
+        appear more than once (learn() only reads it). lr, gamma, betas, eps, seed and noise_seed are each one
+        value applied to every member or a sequence of M; noise_seed=None gives each member its minibatch seed
+        (DeviceNoise(None)'s rule). batch_size is shared."""
+        torch = require_gpu(type(self).__name__)
+        self._torch, self._nat = torch, _native
+        nets, replays = list(nets), list(replays)
+        M = len(nets)
+        if not 1 <= M <= MAX_MEMBERS:
+            raise ValueError(f"a population has 1..{MAX_MEMBERS} members, got {M}")
+        if len(replays) != M:
+            raise ValueError(f"{M} nets need {M} replays (one replay may appear more than once), got {len(replays)}")
+        for r in replays:
+            if isinstance(r, PrioritizedRainbowReplay):
+                raise ValueError("a RainbowPopulation has no prioritized members: a PrioritizedRainbowReplay takes a "
+                                 "PrioritizedRainbowLearner of its own")
+            if not isinstance(r, RainbowReplay):
+                raise ValueError(f"expected RainbowReplays, got a {type(r).__name__}")
+        self.device = cuda_device(torch, device, replays[0].device)
+        for r in replays:
+            if r.device != self.device:
+                raise ValueError(f"a replay lives on {r.device}, the population on {self.device}")
+            if r.capacity != replays[0].capacity:
+                raise ValueError("the replays of a population share one capacity")
+        self.replays = replays
+        lib = _native.lib
+        self.batch_size = int(batch_size)
+        one = int(lib.mg_rainbow_learn_scratch_bytes(self.batch_size))
+        if one == 0:
+            raise ValueError("batch_size must be in 1..1024")
+        lrs, gammas, epss = (per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
+        seeds, pairs = per_member(seed, M, "seed"), per_member(betas, M, "betas", pair=True)
+        nseeds = seeds if noise_seed is None else per_member(noise_seed, M, "noise_seed")
+        self._members = (_native.DqnMember * M)()
+        for m in range(M):
+            self._members[m] = _native.DqnMember(
+                replays[m].memory.data_ptr(), replays[m]._counter.data_ptr(), int(seeds[m]) & U64, 0, 0,
+                _native.DqnHyper(float(lrs[m]), float(gammas[m]), float(pairs[m][0]), float(pairs[m][1]),
+                                 float(epss[m]), 1, 0))
+        self._noise_seeds = (ctypes.c_uint64 * M)(*(int(s) & U64 for s in nseeds))
+        assert int(lib.mg_rainbow_learner_bytes()) == 4 * LEARNER_FLOATS
+        states = [n.state if isinstance(n, RainbowNet) else n for n in nets]
+        self._buf = torch.stack([learner_array(sd) for sd in states]).to(self.device)
+        self._scratch_bytes = one * M
+        self._scratch = torch.empty(self._scratch_bytes // 4, dtype=torch.float32, device=self.device)
+        self._stride = int(lib.mg_rainbow_packed_bytes())
+        self._packed = torch.empty((M, self._stride), dtype=torch.uint8, device=self.device)
+        self._table_bytes = int(lib.mg_rainbow_learn_many_table_bytes(M))
+        self._table = torch.empty(self._table_bytes, dtype=torch.uint8, device=self.device)
+        self._write_table()
+        # the acting nets: `packed` is row m of the one buffer every learn() rewrites, `state` is read back lazily
+        self.nets = []
+        for m in range(M):
+            net = _LearnerNet(model_state_dict(self._buf[m], 0), training=True, device=self.device)
+            net._learner = _Member(self, m)
+            self.nets.append(net)
+        self._call(0)
+
+    # ------------------------------------------------------------------ helpers
+    def __len__(self):
+        return len(self._members)
+
+    def _stream(self):
+        return raw_stream(self._torch, self.device)
+
+    def _index(self, m):
+        """Member index m as an int in 0 .. M - 1; anything else (a negative one too) is an IndexError."""
+        M = len(self._members)
+        if not 0 <= int(m) < M:
+            raise IndexError(f"member {m} of a population of {M}")
+        return int(m)
+
+    def _write_table(self):
+        """The device's member table (replays, seeds, gamma, Adam's constants) from the member list."""
+        _native.check(_native.lib.mg_rainbow_learn_many_init(self._table.data_ptr(), self._table_bytes, self._members,
+                                                             len(self._members), self._stream()),
+                      "mg_rainbow_learn_many_init")
+
+    def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None):
+        """One call of mg_rainbow_learn_many (U == 0: the effective weights and the pack alone); on success it
+        has advanced the members' counters."""
+        rc = _native.lib.mg_rainbow_learn_many(
+            self._buf.data_ptr(), self._table.data_ptr(), self._table_bytes, self._members, len(self._members),
+            self.replays[0].capacity, self.batch_size, U, ptr(noise), ptr(loss), ptr(rows), ptr(proj), ptr(grads),
+            self._packed.data_ptr(), self._stride, self._scratch.data_ptr(), self._scratch_bytes, self._stream())
+        _native.check(rc, "mg_rainbow_learn_many")
+        for net in self.nets:
+            net._stale = True
+
+    @property
+    def learn_step_counter(self):
+        """Per member, the updates made so far (Adam's step count, the noise stream's update index)."""
+        return [int(e.first_update) for e in self._members]
+
+    @property
+    def draw_counter(self):
+        """Per member, the minibatches drawn so far."""
+        return [int(e.first_draw) for e in self._members]
+
+    @property
+    def seed(self):
+        return [int(e.seed) for e in self._members]
+
+    @property
+    def noise_seed(self):
+        return [int(s) for s in self._noise_seeds]
+
+    # ------------------------------------------------------------------ learn
+    def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
+              return_proj: bool = False, return_grads: bool = False):
+        """num_updates times compute_td_loss for every member, enqueued back to back on the current stream: one
+        launch for all the noise factors, seven per update of the whole population, one for the acting nets;
+        nothing is synchronised and nothing is drawn or uploaded by the host. Returns None, the one requested
+        device tensor, or a tuple of the requested ones in the order loss [U, M], rows [U, M, B, 24], proj
+        [U, M, B, 51], grads [U, M, P]."""
+        torch = self._torch
+        U, M, B = int(num_updates), len(self._members), self.batch_size
+        if U < 0:
+            raise ValueError("num_updates must be >= 0")
+        new = lambda want, *shape: torch.empty(shape, dtype=torch.float32, device=self.device) if want else None  # noqa: E731
+        loss, rows = new(return_loss, U, M), new(return_rows, U, M, B, ROW)
+        proj, grads = new(return_proj, U, M, B, NUM_ATOMS), new(return_grads, U, M, NUM_PARAMS)
+        if U > 0:
+            noise = torch.empty((U, M, 2, NUM_FACTORS), dtype=torch.float32, device=self.device)
+            first = (ctypes.c_uint64 * M)(*(e.first_update for e in self._members))
+            rc = _native.lib.mg_rainbow_noise_many(self._noise_seeds, first, M, U, noise.data_ptr(), self._stream())
+            _native.check(rc, "mg_rainbow_noise_many")
+            self._call(U, noise, loss, rows, proj, grads)  # `noise` may go: the allocator is stream-ordered
+        out = tuple(t for t in (loss, rows, proj, grads) if t is not None)
+        return None if not out else out[0] if len(out) == 1 else out
+
+    def sync_target(self, members=None):
+        """update_target (:551-552, :690-691) -- target := current, noise included -- for all members or for an
+        iterable of member indices, in one launch."""
+        M = len(self._members)
+        mask = 0
+        for m in range(M) if members is None else members:
+            mask |= 1 << self._index(m)
+        rc = _native.lib.mg_rainbow_sync_target_many(self._buf.data_ptr(), M, mask, self._stream())
+        _native.check(rc, "mg_rainbow_sync_target_many")
+
+    # ------------------------------------------------------------------ checkpoints
+    def current_state_dict(self, m):
+        """Member m's current_model.state_dict() as ranbowdqn.py:699 saves it (copies, torch-loadable)."""
+        return model_state_dict(self._buf[self._index(m)], 0)
+
+    def target_state_dict(self, m):
+        return model_state_dict(self._buf[self._index(m)], 1)
+
+    def member_state_dict(self, m):
+        """Exactly the state_dict() of the lone RainbowLearner(..., generator=DeviceNoise(noise_seed[m])) member m
+        equals: it loads into one."""
+        m = self._index(m)
+        e = self._members[m]
+        return {"learner": self._buf[m].clone(), "learn_step_counter": int(e.first_update),
+                "draw_counter": int(e.first_draw), "seed": int(e.seed), "noise": "device",
+                "noise_seed": int(self._noise_seeds[m])}
+
+    @staticmethod
+    def _device_noise_state(sd):
+        if sd.get("noise", "torch") != "device":
+            raise ValueError('the state is of a learner with "torch" noise; a population draws "device" noise '
+                             "(a RainbowLearner built with generator=DeviceNoise(...))")
+
+    def _take_member(self, m, buf, step, draw, seed, noise_seed):
+        self._buf[m].copy_(self._torch.as_tensor(buf).to(self._torch.float32).reshape(-1))
+        e = self._members[m]
+        e.first_update, e.first_draw, e.seed = int(step), int(draw), int(seed) & U64
+        self._noise_seeds[m] = int(noise_seed) & U64
+
+    def load_member_state_dict(self, m, sd):
+        """A device-noise RainbowLearner's state_dict() (or member_state_dict()) into member m: nets, noise,
+        moments, counters and seeds."""
+        m = self._index(m)
+        self._device_noise_state(sd)
+        if self._torch.as_tensor(sd["learner"]).numel() != LEARNER_FLOATS:
+            raise ValueError("expected the state of a RainbowLearner")
+        self._take_member(m, sd["learner"], sd["learn_step_counter"], sd["draw_counter"], sd["seed"],
+                          sd["noise_seed"])
+        self._write_table()
+        self._call(0)
+
+    def state_dict(self):
+        """Every member's models with their noise, moments, counters and seeds: a run resumed from it continues
+        bit for bit."""
+        return {"learners": self._buf.clone(), "learn_step_counter": self.learn_step_counter,
+                "draw_counter": self.draw_counter, "seed": self.seed, "noise": "device",
+                "noise_seed": self.noise_seed}
+
+    def load_state_dict(self, sd):
+        self._device_noise_state(sd)
+        buf = self._torch.as_tensor(sd["learners"])
+        if tuple(buf.shape) != tuple(self._buf.shape):
+            raise ValueError(f"expected the state of {len(self)} Rainbow learners")
+        for m in range(len(self)):
+            self._take_member(m, buf[m], sd["learn_step_counter"][m], sd["draw_counter"][m], sd["seed"][m],
+                              sd["noise_seed"][m])
+        self._write_table()
+        self._call(0)
+
+    def copy_member(self, src, dst):
+        """Population-based training's exploit step: dst takes src's nets, noise blocks, Adam moments and counters
+        (a device-side copy) and is repacked for acting; it keeps its own seeds, replay and hyperparameters."""
+        src, dst = self._index(src), self._index(dst)
+        if src == dst:
+            return
+        self._buf[dst].copy_(self._buf[src])
+        self._members[dst].first_update = self._members[src].first_update
+        self._members[dst].first_draw = self._members[src].first_draw
+        self._call(0)
