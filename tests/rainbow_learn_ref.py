@@ -192,6 +192,44 @@ def sequence(run, L0, ring, counter, B, seed=3):
     return L, out1 + out2
 
 
+# The batch edges with real gradients: one row, a wave and a row, the first batch past one block of items, the
+# largest batch. The "soft" family: "default" saturates the softmax, and at B = 1 its gradient is exactly zero.
+EDGE_BATCHES = (1, 33, 257, 1024)
+# The minibatch seed of those cases. 25 of replay_rows(64)'s rows have no gradient at all: a done row whose
+# clamped reward falls on an atom has l == u in the projection, both shares are zero and its mass is dropped, as
+# in the reference, so proj is zero and so is the loss. With one row per update the seed decides whether an update
+# draws such a row; 36 is the first seed from 3 (sequence()'s default) on whose three draws have a gradient on
+# both RINGS, chosen by the restatement, not by the library.
+EDGE_SEED = 36
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(batch, capacity, counter):
+    """The restatement's sequence() from the "soft" golden state under EDGE_SEED, computed once for the host and
+    the device test (read-only arrays), after its own check that every one of the three updates is a real one: a
+    gradient with non-zero entries, and current parameters that moved. The parameters after each update come
+    from the restatement run one update per call, whose end has to be sequence()'s end bit for bit."""
+    L0 = learner_numpy(golden_state(1, "soft"))
+    ring, c = ring_case(capacity, counter)
+    want = sequence(run_ref, L0, ring, c, batch, seed=EDGE_SEED)
+    nf, L, moved, nonzero = noise(3), L0, [], []
+    for u in range(3):
+        if u == 2:
+            L = L.copy()
+            sync_target(L)
+        after, _, _, _, grads = run_ref(L, ring, c, batch, 1, u, EDGE_SEED, u, nf[u:u + 1])
+        assert np.array_equal(bits(grads[0]), bits((want[1][3][u] if u < 2 else want[1][7][0]))), u
+        moved.append(int(np.count_nonzero(bits(after[:NP]) != bits(L[:NP]))))
+        nonzero.append(int(np.count_nonzero(grads[0])))
+        L = after
+    assert np.array_equal(bits(L), bits(want[0]))
+    print(f"B {batch}, ring {(capacity, counter)}: non-zero gradients per update {nonzero}, parameters moved {moved}")
+    assert min(nonzero) > 0 and min(moved) > 0, (nonzero, moved)
+    for a in (want[0], *want[1]):
+        a.setflags(write=False)
+    return L0, want
+
+
 NAMES = ("loss", "rows", "proj", "grads") * 2
 BLOCKS = (("current", 0, NP), ("target", NP, 2 * NP), ("m", 2 * NP, 3 * NP), ("v", 3 * NP, 4 * NP),
           ("noise current", 4 * NP, 4 * NP + NE), ("noise target", 4 * NP + NE, 4 * NP + 2 * NE))

@@ -1,10 +1,12 @@
 """Prioritized replay on the GPU: mg_per_store / mg_per_sample / mg_per_update against the host twins bit for
-bit (rows, counter, every node of both trees, max_priority, indices and weights), the alpha = 1 rounds of the
-reference's fixture on the device, mg_rainbow_learn_prioritized against its host twin, and the Python class's
-checkpoint."""
+bit (rows, counter, every node of both trees, max_priority, indices and weights), the same at the capacities
+where the launch path changes against the one-push-at-a-time model of tests/per_model.py too, the alpha = 1
+rounds of the reference's fixture on the device, mg_rainbow_learn_prioritized against its host twin, and the
+Python class's checkpoint."""
 import numpy as np
 import pytest
 
+import per_model as M
 import per_ref as P
 import rainbow_learn_ref as R
 from learn_ref import bits
@@ -87,6 +89,104 @@ def test_batches_with_heavy_duplicates(torch, batch):
     assert batch == 1 or len(set(hidx.tolist())) < batch
 
 
+class _DeviceAndHost:
+    """The device buffer and its host twin behind the calls per_model.run_scenario makes: every call goes to both,
+    the samples have to be the same bits, and the device's results are what the model is compared with."""
+
+    def __init__(self, torch, cap, alpha):
+        self.torch, self.rp, self.h = torch, _device(torch, cap, alpha), P.HostPer(cap, alpha)
+
+    def store(self, tr):
+        _store(self.torch, self.rp, tr)
+        self.h.store(tr)
+
+    def update(self, idx, prio):
+        self.rp.update_priorities(self.torch.from_numpy(idx), self.torch.from_numpy(prio))
+        self.h.update(idx, prio)
+
+    def sample(self, batch, beta, seed, draw):
+        idx, w = (t.cpu().numpy() for t in self.rp.sample_indices(batch, beta, seed=seed, draw=draw))
+        hidx, hw = self.h.sample(batch, beta, seed, draw)
+        assert np.array_equal(idx, hidx) and np.array_equal(bits(w), bits(hw)), (beta, draw)
+        return idx, w
+
+    def state(self):
+        return self.rp._tree.cpu().numpy(), int(self.rp._counter.item())
+
+    def same_state(self, what):
+        _assert_same_state(self.rp, self.h, what)
+
+
+# capacity: the launch path the scenario's stores reach on the device (the levels are the tail level of the store
+# that fills the ring, asserted below)
+EDGES = {1: "logC == 0: the fill alone, no level and no tail launch",
+         2: "one level, in the tail",
+         4: "C == capacity: no leaf beyond the ring",
+         1025: "one past a power of two: 1023 leaves beyond the ring, every level in the tail",
+         4096: "C == capacity over several blocks, tail level 3",
+         5000: "tail level 3: two per-level launches, and the whole-ring store's two wrapped segments span several "
+               "blocks each",
+         9000: "tail level 4: three per-level launches"}
+TAIL_LEVELS = {1: 1, 2: 1, 4: 1, 1025: 1, 4096: 3, 5000: 3, 9000: 4}
+
+
+def test_the_edge_capacities_are_on_their_launch_paths():
+    """The tail level of the store that fills each ring, from the library's own constants (per_model.tail_level
+    reads them from csrc/mg_per.h), and the whole-ring store's start at capacity 5000: if the constants move,
+    this fails before the cases below quietly leave their paths."""
+    from merging_gym import _native
+
+    assert {cap: M.tail_level(cap) for cap in EDGES} == TAIL_LEVELS
+    assert (M.tail_level(4083), M.tail_level(4084), M.tail_level(8167), M.tail_level(8168)) == (2, 3, 3, 4)
+    assert M.tail_level(3000) == 2  # the largest ring of the tests above: one per-level launch
+    for cap in EDGES:
+        C = _native.lib.mg_per_bytes(cap) // 8 // 4  # 8 (4 C + 2) bytes
+        assert (C == cap) == (cap in (1, 2, 4, 4096)) and (C == 1) == (cap == 1)
+    stores = M.scenario_stores(5000)
+    start = sum(n * T for n, T in stores[:3]) % 5000
+    assert stores[3] == (5000, 1) and min(start, 5000 - start) > 3 * 256  # both segments: more than three blocks
+
+
+@pytest.mark.parametrize("alpha", M.ALPHAS)
+@pytest.mark.parametrize("cap", tuple(EDGES))
+def test_edge_capacities_equal_the_host_twins_and_the_model(torch, cap, alpha):
+    """per_model.run_scenario on the device: the stores of per_model.scenario_stores (one of exactly the ring from
+    a non-zero position, one larger than the ring), after each one updates of 1, 33 and 1024 entries with
+    duplicates and rejected entries, and samples at beta 0.4 and 1.0. After every store and update the rows, the
+    counter and every tree double equal the host twin's bit for bit, and every tree node and max_priority equal
+    the one-push-at-a-time model's; the samples equal the host twin's bit for bit, the model's indices exactly
+    and its weights within 1 fp32 step. EDGES[cap] names the launch path the capacity is here for."""
+    both = _DeviceAndHost(torch, cap, alpha)
+    both.same_state("fresh")
+    model, worst = M.run_scenario(cap, alpha, both, after=both.same_state)
+    print(f"capacity {cap} ({EDGES[cap]}), alpha {alpha}: worst weight distance {worst} fp32 steps")
+    assert worst <= 1
+    assert len(both.rp) == cap and both.rp.max_priority == model.max_priority
+
+
+def test_capacity_one_on_the_device(torch):
+    """PrioritizedRainbowReplay takes capacity 1 (RainbowReplay refuses only capacity < 1): one leaf that is the
+    root, len < 2 for ever, so every draw is slot 0 with weight 1 and sample() refuses."""
+    from merging_gym import RainbowReplay
+
+    with pytest.raises(ValueError, match="capacity must be >= 1"):
+        RainbowReplay(0, device=DEV)
+    rp, h = _device(torch, 1, 0.6), P.HostPer(1, 0.6)
+    for tr in (P.transitions(1, 1), P.transitions(2, 2, first=1)):
+        _store(torch, rp, tr)
+        h.store(tr)
+    _assert_same_state(rp, h, "stores")
+    assert np.array_equal(rp.memory.cpu().numpy()[0], P.expected_row(4))
+    idx, w = rp.sample_indices(7, 0.4, seed=3, draw=0)
+    assert idx.tolist() == [0] * 7 and w.tolist() == [1.0] * 7
+    rp.update_priorities([0, 1, -1, 0], [2.0, 5.0, 5.0, -1.0])
+    h.update([0, 1, -1, 0], [2.0, 5.0, 5.0, -1.0])
+    _assert_same_state(rp, h, "update")
+    assert len(rp) == 1 and rp.max_priority == 2.0 and rp._tree[1].item() == P.host_pow([2.0], [0.6])[0]
+    with pytest.raises(ValueError, match="at least two stored transitions"):
+        rp.sample(4, 0.4)
+
+
 @pytest.mark.parametrize("size", (6, 13))
 def test_alpha_one_fixture_rounds_on_the_device(torch, size):
     """The reference's own trees, S aside (the host twin pins it), bit for bit after every round."""
@@ -167,22 +267,51 @@ def test_three_updates_in_one_call_equal_three_calls_of_one(torch):
     assert len(np.unique(a[4].cpu().numpy())) > 4  # a real sample
 
 
-@pytest.mark.parametrize("size,alpha", ((13, 1.0), (13, 0.6), (3000, 1.0), (3000, 0.6)))
-def test_prioritized_learner_equals_its_host_twin(torch, size, alpha):
+def _learner_against_its_host_twin(torch, size, alpha, B):
+    """Three updates in one call from P.learn_case(size, alpha), beta 0.5: the learner buffer, all six outputs,
+    every tree node and max_priority, the rows and the counter bit for bit, and the packed acting net. Returns
+    the host twin's tuple and the tree before and after the call."""
     from merging_gym import RainbowNet
 
-    B, U, beta, eps = 32, 3, 0.5, 1e-5
+    U, beta, eps = 3, 0.5, 1e-5
     h = P.learn_case(size, alpha)
+    before = h.tree.copy()
     lr = _prioritized(torch, h, B, eps)
     rp, sd = lr.replay, R.golden_state(1, "soft")
     got = [t.cpu().numpy() for t in _learn_all(lr, U, beta)]
     want = P.run_host_prioritized(R.learner_numpy(sd), h, B, U, beta, eps, seed=3, noise_f=R.noise(U))
     R.assert_same((lr._buf.cpu().numpy(), got[:4]), (want[0], list(want[1:5])))
     assert np.array_equal(got[4], want[5]) and np.array_equal(bits(got[5]), bits(want[6]))
-    assert len(np.unique(want[6])) > 4 and (want[6] <= 1.0).all()  # real weights
     _assert_same_state(rp, h, "after learn")
+    assert rp.max_priority == h.max_priority
     # the acting net equals mg_rainbow_pack of the result
     assert torch.equal(RainbowNet.from_state_dict(lr.current_state_dict(), device=DEV).packed, lr.net.packed)
+    return want, before, h.tree
+
+
+@pytest.mark.parametrize("size,alpha", ((13, 1.0), (13, 0.6), (3000, 1.0), (3000, 0.6)))
+def test_prioritized_learner_equals_its_host_twin(torch, size, alpha):
+    want, _, _ = _learner_against_its_host_twin(torch, size, alpha, 32)
+    assert len(np.unique(want[6])) > 4 and (want[6] <= 1.0).all()  # real weights
+
+
+@pytest.mark.parametrize("B,size,alpha", ((1, 13, 0.6), (33, 13, 0.6), (1024, 13, 1.0)),
+                         ids=("one-row", "wave-and-a-row", "full-block"))
+def test_prioritized_learner_at_the_batch_edges(torch, B, size, alpha):
+    """The sample, the weighted update and the in-call priority write-back (loss_b + prio_eps into the tree) at
+    B = 1, at a batch that is no multiple of a wave, and at B = 1024 = the update kernel's block, where its LDS
+    arrays, its duplicate scan and its max reduction are full: on the ring of 13 at most 12 slots can be drawn,
+    so the 1024 entries name each drawn slot 85 times on average (the heaviest several hundred times) and only the
+    last valid entry of each may set the leaf."""
+    want, before, after = _learner_against_its_host_twin(torch, size, alpha, B)
+    idx, w, grads = want[5], want[6], want[4]
+    assert (w > 0).all() and (w <= 1.0).all() and (B == 1 or len(np.unique(w)) > 4)  # real weights
+    # real gradients: in every update, but for one row alone, which may be a row without one (R.EDGE_SEED's comment)
+    assert (any if B == 1 else all)(np.count_nonzero(g) > 0 for g in grads)
+    assert not np.array_equal(P.f64bits(after), P.f64bits(before))  # the priorities moved
+    if B == 1024:
+        counts = np.bincount(idx[0], minlength=size)
+        assert counts[size - 1] == 0 and counts.sum() == B and counts.max() > 64 and np.count_nonzero(counts) > 4
 
 
 def test_checkpoint_resumes_bit_for_bit(torch):

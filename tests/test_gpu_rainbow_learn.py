@@ -43,7 +43,9 @@ def _all(learner, U):
 @pytest.mark.parametrize("capacity,counter", R.RINGS, ids=["partly-filled", "wrapped"])
 @pytest.mark.parametrize("batch", R.BATCHES)
 def test_device_learn_equals_the_restatement(torch, batch, capacity, counter):
-    """learn(2), sync_target(), learn(1) on the cases of tests/test_rainbow_learn_host.py."""
+    """learn(2), sync_target(), learn(1) on the cases of tests/test_rainbow_learn_host.py. The "default" family
+    at B = 1 is kept as the saturated-softmax case: a zero-gradient update (see that file); the edge batches
+    with real gradients are the test below."""
     fam = "soft" if batch in (32, 128) else "default"
     ring, c = R.ring_case(capacity, counter)
     want = R.sequence(R.run_ref, R.learner_numpy(R.golden_state(1, fam)), ring, c, batch)
@@ -52,6 +54,28 @@ def test_device_learn_equals_the_restatement(torch, batch, capacity, counter):
     lr.sync_target()
     out += _all(lr, 1)
     R.assert_same((lr._buf.cpu().numpy(), out), want)
+    assert (lr.learn_step_counter, lr.draw_counter) == (3, 3)
+
+
+@pytest.mark.parametrize("capacity,counter", R.RINGS, ids=["partly-filled", "wrapped"])
+@pytest.mark.parametrize("batch", R.EDGE_BATCHES)
+def test_device_learn_equals_the_restatement_at_batch_edges(torch, batch, capacity, counter):
+    """The same sequence from the "soft" state at B = 1, 33, 257 (the first batch past one block of items) and
+    1024 (the largest): the backward and Adam launches of the lone learner on real gradients. Every update's
+    gradient has non-zero entries, and the current parameters moved: the parameters after the first call differ
+    from the start's, those after the second from the first call's (R.edge_reference checks the restatement,
+    which the device equals bit for bit, update by update)."""
+    L0, want = R.edge_reference(batch, capacity, counter)
+    lr = _learner(torch, "soft", *R.ring_case(capacity, counter), batch, seed=R.EDGE_SEED)
+    out = _all(lr, 2)
+    mid = lr._buf[:R.NP].cpu().numpy()
+    lr.sync_target()
+    out += _all(lr, 1)
+    end = lr._buf.cpu().numpy()
+    R.assert_same((end, out), want)
+    for grads in (out[3][0], out[3][1], out[7][0]):
+        assert np.count_nonzero(grads) > 0 and np.isfinite(grads).all()
+    assert (bits(mid) != bits(L0[:R.NP])).any() and (bits(end[:R.NP]) != bits(mid)).any()
     assert (lr.learn_step_counter, lr.draw_counter) == (3, 3)
 
 

@@ -22,13 +22,30 @@ def learner0():
 @pytest.mark.parametrize("batch", R.BATCHES)
 def test_host_twin_equals_the_restatement(learner0, batch, capacity, counter):
     """learn(2), sync_target(), learn(1): current, target, m, v, both noise blocks, every loss, sampled row,
-    proj and gradient."""
+    proj and gradient. The "default" family at B = 1 is kept as the saturated-softmax case: its first update's
+    gradient is exactly zero and no parameter moves (host twin, wrapped ring, measured), and at B = 33 the
+    largest gradient entry is 2e-4. The edge batches with real gradients are the test below."""
     fam = "soft" if batch in (32, 128) else "default"
     ring, c = R.ring_case(capacity, counter)
     want = R.sequence(R.run_ref, learner0[fam], ring, c, batch)
     got = R.sequence(R.run_host, learner0[fam], ring, c, batch)
     R.assert_same(got, want)
     assert np.isfinite(want[1][0]).all() and np.abs(want[1][3]).max() > 0  # a real update: finite loss, gradients
+
+
+@pytest.mark.parametrize("capacity,counter", R.RINGS, ids=["partly-filled", "wrapped"])
+@pytest.mark.parametrize("batch", R.EDGE_BATCHES)
+def test_host_twin_equals_the_restatement_at_batch_edges(batch, capacity, counter):
+    """The same sequence from the "soft" state at B = 1, 33, 257 (the first batch past one block of items) and
+    1024 (the largest). Every update's gradient has non-zero entries and moves the current parameters
+    (R.edge_reference checks the latter update by update), so none of these cases passes on zeros."""
+    L0, want = R.edge_reference(batch, capacity, counter)
+    got = R.sequence(R.run_host, L0, *R.ring_case(capacity, counter), batch, seed=R.EDGE_SEED)
+    R.assert_same(got, want)
+    for grads in (got[1][3][0], got[1][3][1], got[1][7][0]):
+        assert np.count_nonzero(grads) > 0 and np.isfinite(grads).all()
+    assert np.isfinite(got[1][0]).all() and np.isfinite(got[1][4]).all()
+    assert (bits(got[0][:R.NP]) != bits(L0[:R.NP])).any()
 
 
 def test_sampled_rows_are_the_filled_rows_only():
