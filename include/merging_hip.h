@@ -61,6 +61,10 @@
  *   mg_rainbow_noise / mg_host_rainbow_noise / mg_rainbow_ndtri / mg_host_rainbow_ndtri: the factors of
  *                     RainbowDQN.reset_noise (:486-496, :537-541) drawn on the device from a counter-based
  *                     stream in a documented order, and its inverse normal CDF alone
+ *   mg_rollout_rainbow_many / mg_rainbow_replay_store_many / mg_host_rainbow_replay_store_many: the acting
+ *                     half of a Rainbow population -- up to 64 members' rollouts on slices of one env batch
+ *                     in one launch, and their transitions into 64 replay memories in two; every member bit
+ *                     for bit a lone mg_rollout_rainbow / mg_rainbow_replay_store
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -792,6 +796,27 @@ int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_
 int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n);
 int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
 
+/* ---- a Rainbow population acting in one launch (additive to ABI 21) ----------------------------------
+ * mg_rollout_rainbow for `members` (1 .. 64) actors on ONE env batch of n = members * n_member envs: member m
+ * owns envs [m n_member, (m + 1) n_member) and acts there with its own packed net nets[m] (a host array of
+ * `members` device pointers, each 16-byte aligned; read during the call only). state, traj and stats are the
+ * whole batch's ([T, n, ...] trajectory rows, ceil(n / 64) won-mask words per step); params, opponent_mode,
+ * num_steps and flags are shared. There is no draw, so there are no seeds and no env_offset: member m is bit
+ * for bit mg_rollout_rainbow with nets[m] on its slice alone (n = n_member) -- trajectory rows, env state,
+ * episode records and won bits. The member is a grid dimension: members * ceil(n_member / 512) blocks, each
+ * copying its member's net into LDS, the nets' addresses in the kernel argument, so a call allocates and
+ * synchronises nothing. n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole,
+ * so two members never share a wave or a word). opponent_mode 0 or 2 as mg_rollout_rainbow; cross-play (a
+ * member against another member's net) is not offered: two Rainbow nets and the observation tile exceed one
+ * CU's LDS. Refused before anything is read or launched, in this order: members outside 1 .. 64, n_member < 0,
+ * n_member % 64 != 0, members * n_member past the grid limit, what mg_rollout_rainbow refuses of params, state
+ * and traj, nets NULL, a NULL or misaligned member net (the text names the member), num_steps outside
+ * 0 .. 65535, opponent_mode other than 0 or 2, a misaligned traj buffer; then n_member == 0 or num_steps == 0
+ * returns 0 and launches nothing. */
+int mg_rollout_rainbow_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                            const mg_stats* stats, int64_t n_member, int32_t members, int32_t num_steps,
+                            const void* const* nets, int32_t opponent_mode, uint32_t flags, void* stream);
+
 /* ---- Rainbow learning (additive to ABI 21) ----------------------------------------------------------
  * compute_td_loss (scripts/ranbowdqn.py:584-609) with projection_distribution (:554-582) on the device, and
  * the (s, a, r, s', done) ReplayBuffer (:265-323) it samples from.
@@ -858,6 +883,29 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
  * mg_host_rainbow_log: y[i] = that log of x[i] for normal positive x (NaN otherwise). */
 int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
                             int32_t num_steps, void* stream);
+/* (additive to ABI 21) mg_rainbow_replay_store for `members` (1 .. 64) replay memories from ONE [T, N, ...]
+ * mg_transitions, N = members * n_member: rows[m] / counters[m] are host arrays of device pointers (read during
+ * the call only). Member m's transition k = t n_member + j (0 <= j < n_member) reads column c = m n_member + j
+ * of the tensors in place -- s = obs_first[c] at t = 0, else obs[t - 1, c]; s' = final_obs[t, c] where done (and
+ * final_obs is given), else obs[t, c]; a and done from a1 / done or flags at [t, c]; r = rew[t, c, 0] -- and goes
+ * to slot (counter_m + k) % capacity of rows[m]. With total_m = T n_member > capacity only the member's newest
+ * `capacity` transitions (k >= total_m - capacity) are written, per member. Then counter_m += T n_member: exactly
+ * what mg_rainbow_replay_store leaves when given a contiguous copy of the slice. Two launches for all members:
+ * the store on a grid (ceil(T n_member / 256), members) with the members' pointers in the kernel argument, then
+ * one thread per member moves its counter. The store reads no won mask, so any n_member >= 0 is accepted.
+ * capacity is shared. Refused before anything is read or launched, in this order: members outside 1 .. 64; rows,
+ * counters or tr NULL; member by member a NULL rows / counter, one not 8-byte aligned, a ring or counter listed
+ * twice (two members' appends to one ring have no defined order); capacity outside 1 .. 2^32; n_member < 0 or
+ * num_steps < 0; a non-NULL goal / next_goal / reward / meta_goal; then n_member == 0 or num_steps == 0 returns
+ * 0; then a missing obs_first / obs / a1 (or flags) / rew, a float buffer not 4-byte aligned, n_member *
+ * num_steps past the grid limit. Appending from inside the rollout kernel and prioritized members (whose trees
+ * need mg_per_store) are not offered.
+ * mg_host_rainbow_replay_store_many: the same functions on HOST pointers, synchronously. */
+int mg_rainbow_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                                 const mg_transitions* tr, int64_t n_member, int32_t num_steps, void* stream);
+int mg_host_rainbow_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members,
+                                      int64_t capacity, const mg_transitions* tr, int64_t n_member,
+                                      int32_t num_steps);
 size_t mg_rainbow_learner_bytes(void);
 size_t mg_rainbow_learn_scratch_bytes(int32_t batch);
 int mg_rainbow_learn(float* learner, const float* rows, const uint64_t* counter, int64_t capacity, int32_t batch,

@@ -35,7 +35,7 @@
 #include "mg_rainbow.h"         // Rainbow's acting net: pack kernel, MFMA forward, the fp32 head
 #include "mg_rollout_qnet.h"    // config 5: qnet_rollout_ws_kernel, lone and with the member in the grid, their host side
 #include "mg_rollout_hdqn.h"    // the h-DQN acting loop: hdqn_rollout_kernel
-#include "mg_rollout_rainbow.h" // Rainbow's acting loop: rainbow_rollout_kernel
+#include "mg_rollout_rainbow.h" // Rainbow's acting loop: rainbow_rollout_kernel, lone and with the member in the grid
 #include "mg_reset_observe.h"   // reset_kernel, observe_kernel
 #include "mg_replay.h"          // the replay ring: scan, write and sample kernels, counter_add_kernel, the stores' host side
 #include "mg_launch.h"          // error text, armed events, argument checks, launch helpers
@@ -583,26 +583,44 @@ int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_
                        void* stream) {
   if (int e = check_rollout_args(params, state, traj, n)) return e;
   if (int e = check_packed_net(net, "mg_rollout_rainbow: net must be a 16-byte aligned packed Rainbow net")) return e;
-  if (num_steps < 0 || num_steps > 65535)
-    return fail(hipErrorInvalidValue, "%s", "need 0 <= num_steps <= 65535 (split longer rollouts)");
-  if (opponent_mode != 0 && opponent_mode != 2)
-    return fail(hipErrorInvalidValue, "%s",
-                "mg_rollout_rainbow: opponent_mode must be 0 (None) or 2 (the same net on state[3:] + state[:3])");
+  if (int e = check_rb_rollout_steps_mode(false, num_steps, opponent_mode)) return e;
   if (int e = check_traj(traj)) return e;
   if (n == 0 || num_steps == 0) return 0;
-  RbRollout R{};
-  R.P = *params;
-  R.R0 = reset0(*params);
-  R.S = *state;
-  R.T = *traj;
-  if (stats) R.St = *stats;
+  RbRollout R = make_rb_rollout(params, state, traj, stats, n, num_steps, flags);
   R.net = static_cast<const uint8_t*>(net);
-  R.n = n;
-  R.num_steps = num_steps;
-  R.flags = flags;
-  launch(opponent_mode == 0 ? rainbow_rollout_kernel<0> : rainbow_rollout_kernel<2>, grid_blocks(n, kRbThreads),
-         kRbThreads, static_cast<hipStream_t>(stream), R);
+  launch(rainbow_rollout_instance<false>(opponent_mode), grid_blocks(n, kRbThreads), kRbThreads,
+         static_cast<hipStream_t>(stream), R);
   return finish_launch("mg_rollout_rainbow");
+}
+
+int mg_rollout_rainbow_many(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                            int64_t n_member, int32_t members, int32_t num_steps, const void* const* nets,
+                            int32_t opponent_mode, uint32_t flags, void* stream) {
+  const char* const who = "mg_rollout_rainbow_many: %s";
+  if (!members_ok(members)) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
+  if (n_member < 0) return fail(hipErrorInvalidValue, who, "n_member < 0");
+  if (n_member % 64 != 0)
+    return fail(hipErrorInvalidValue, who,
+                "n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole, so no "
+                "two members may share one)");
+  if (n_member > (static_cast<int64_t>(0x7fffffff) * kBlock) / members)
+    return fail(hipErrorInvalidValue, who, "members * n_member exceeds the grid limit");
+  const int64_t n = n_member * members;
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (!nets) return fail(hipErrorInvalidValue, who, "nets is NULL (members packed Rainbow nets)");
+  for (int m = 0; m < members; ++m)
+    if (!nets[m] || misaligned(nets[m], 15))
+      return fail_member("mg_rollout_rainbow_many", m, "net must be a 16-byte aligned packed Rainbow net");
+  if (int e = check_rb_rollout_steps_mode(true, num_steps, opponent_mode)) return e;
+  if (int e = check_traj(traj)) return e;
+  if (n_member == 0 || num_steps == 0) return 0;
+  RbRolloutMany A{make_rb_rollout(params, state, traj, stats, n, num_steps, flags), n_member,
+                  static_cast<int32_t>(grid_blocks(n_member, kRbThreads)), members};
+  for (int m = 0; m < members; ++m) A.net[m] = static_cast<const uint8_t*>(nets[m]);
+  launch(rainbow_rollout_instance<true>(opponent_mode),
+         static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kRbThreads,
+         static_cast<hipStream_t>(stream), A);
+  return finish_launch("mg_rollout_rainbow_many");
 }
 
 int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n) {
@@ -628,10 +646,30 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n) {
 // ---- Rainbow learning (scripts/ranbowdqn.py:265-323, :551-609) --------------------------------------
 int mg_rainbow_replay_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
                             int32_t num_steps, void* stream) {
-  if (int e = check_rainbow_store("mg_rainbow_replay_store", rows, counter, capacity, tr, n, num_steps)) return e;
+  if (int e = check_rainbow_store("mg_rainbow_replay_store", RlStoreCall{&rows, &counter, 1, capacity, tr, n, num_steps}))
+    return e;
   if (n == 0 || num_steps == 0) return 0;
   rainbow_store(rows, counter, capacity, tr, n, num_steps, nullptr, 0.0, false, static_cast<hipStream_t>(stream));
   return finish_launch("mg_rainbow_replay_store");
+}
+
+int mg_rainbow_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                                 const mg_transitions* tr, int64_t n_member, int32_t num_steps, void* stream) {
+  const RlStoreCall C{rows, counters, members, capacity, tr, n_member, num_steps};
+  if (int e = check_rainbow_store("mg_rainbow_replay_store_many", C, true)) return e;
+  if (n_member == 0 || num_steps == 0) return 0;
+  rainbow_store_many(C, false, static_cast<hipStream_t>(stream));
+  return finish_launch("mg_rainbow_replay_store_many");
+}
+
+int mg_host_rainbow_replay_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                                      const mg_transitions* tr, int64_t n_member, int32_t num_steps) {
+  const RlStoreCall C{rows, counters, members, capacity, tr, n_member, num_steps};
+  if (int e = check_rainbow_store("mg_host_rainbow_replay_store_many", C, true)) return e;
+  g_err[0] = '\0';
+  if (n_member == 0 || num_steps == 0) return 0;
+  rainbow_store_many(C, true, nullptr);
+  return 0;
 }
 
 size_t mg_rainbow_learner_bytes(void) { return static_cast<size_t>(kRlLearner) * sizeof(float); }
@@ -763,7 +801,7 @@ int mg_host_per_init(void* tree, size_t tree_bytes, int64_t capacity) {
 
 int mg_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
                  int32_t num_steps, void* tree, size_t tree_bytes, double alpha, void* stream) {
-  if (int e = check_rainbow_store("mg_per_store", rows, counter, capacity, tr, n, num_steps)) return e;
+  if (int e = check_rainbow_store("mg_per_store", RlStoreCall{&rows, &counter, 1, capacity, tr, n, num_steps})) return e;
   if (int e = check_per_tree("mg_per_store", tree, tree_bytes, capacity)) return e;
   if (int e = check_per_alpha("mg_per_store", alpha)) return e;
   if (n == 0 || num_steps == 0) return 0;
@@ -773,7 +811,8 @@ int mg_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_tran
 
 int mg_host_per_store(float* rows, uint64_t* counter, int64_t capacity, const mg_transitions* tr, int64_t n,
                       int32_t num_steps, void* tree, size_t tree_bytes, double alpha) {
-  if (int e = check_rainbow_store("mg_host_per_store", rows, counter, capacity, tr, n, num_steps)) return e;
+  if (int e = check_rainbow_store("mg_host_per_store", RlStoreCall{&rows, &counter, 1, capacity, tr, n, num_steps}))
+    return e;
   if (int e = check_per_tree("mg_host_per_store", tree, tree_bytes, capacity)) return e;
   if (int e = check_per_alpha("mg_host_per_store", alpha)) return e;
   g_err[0] = '\0';

@@ -31,20 +31,25 @@ struct RlStore {
   int64_t total;  // T n
 };
 
-// transition idx = t n + i of a store (the host twin of the prioritized store runs it too)
-MG_HD void rl_store_at(const RlStore& R, const uint64_t* counter, float* rows, int64_t cap, int64_t idx) {
+// transition idx = t n + i of a store (the host twin of the prioritized store runs it too). The tensors are
+// [T, stride, ...] and the store's envs their columns [col0, col0 + n): the lone stores pass (n, 0), the member
+// store the whole batch's width and the member's first column.
+MG_HD void rl_store_at(const RlStore& R, const uint64_t* counter, float* rows, int64_t cap, int64_t idx,
+                       int64_t stride, int64_t col0) {
   // only the newest `cap` transitions survive sequential pushes: they occupy distinct slots
   const int64_t skip = R.total > cap ? R.total - cap : 0;
   if (idx >= R.total || idx < skip) return;
-  const int64_t i = idx % R.n;
-  const bool done = R.X.flags ? R.X.flags[4 * idx + 2] != 0 : (R.X.done != nullptr && R.X.done[idx] != 0);
-  const float* s = idx < R.n ? R.X.obs_first + i * kObs : R.X.obs + (idx - R.n) * kObs;
-  const float* s2 = (done && R.X.final_obs ? R.X.final_obs : R.X.obs) + idx * kObs;
+  const int64_t t = idx / R.n;
+  const int64_t c = col0 + (idx - t * R.n);  // the column in the tensors
+  const int64_t row = t * stride + c;
+  const bool done = R.X.flags ? R.X.flags[4 * row + 2] != 0 : (R.X.done != nullptr && R.X.done[row] != 0);
+  const float* s = t == 0 ? R.X.obs_first + c * kObs : R.X.obs + (row - stride) * kObs;
+  const float* s2 = (done && R.X.final_obs ? R.X.final_obs : R.X.obs) + row * kObs;
   float v[kRlRow];
 #pragma unroll
   for (int k = 0; k < kObs; ++k) v[k] = s[k], v[kRlColS2 + k] = s2[k];
-  v[kRlColA] = static_cast<float>(R.X.flags ? static_cast<int8_t>(R.X.flags[4 * idx]) : R.X.a1[idx]);
-  v[kRlColR] = R.X.rew[2 * idx];
+  v[kRlColA] = static_cast<float>(R.X.flags ? static_cast<int8_t>(R.X.flags[4 * row]) : R.X.a1[row]);
+  v[kRlColR] = R.X.rew[2 * row];
   v[kRlColDone] = done ? 1.0f : 0.0f;
   v[kRlRow - 1] = 0.0f;
   const uint64_t slot = (*counter + static_cast<uint64_t>(idx)) % static_cast<uint64_t>(cap);
@@ -55,7 +60,33 @@ MG_HD void rl_store_at(const RlStore& R, const uint64_t* counter, float* rows, i
 
 __global__ __launch_bounds__(kBlock) void rl_store_kernel(const RlStore R, const uint64_t* counter, float* rows,
                                                           int64_t cap) {
-  rl_store_at(R, counter, rows, cap, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
+  rl_store_at(R, counter, rows, cap, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, R.n, 0);
+}
+
+// ---- the member in the grid (mg_rainbow_replay_store_many): member m's slice [m n_member, (m + 1) n_member) of one
+// [T, N, ...] batch into ring m, as the lone store would store a contiguous copy of the slice. Every transition is
+// kept, so a member's slots need no scan: grid (ceil(T n_member / kBlock), members), the rings and counters in
+// the kernel argument, then one thread per member moves its counter.
+struct RlStoreMany {
+  RlStore R;  // X: the whole batch; n = n_member; total = T n_member
+  int64_t N;  // the batch's envs, the row stride
+  int64_t cap;
+  int32_t members;
+  float* rows[kMaxMembers];
+  uint64_t* counter[kMaxMembers];
+};
+static_assert(sizeof(RlStoreMany) <= 4096, "HIP's kernel argument limit");
+
+__global__ __launch_bounds__(kBlock) void rl_store_many_kernel(const RlStoreMany A) {
+  const int m = blockIdx.y;
+  rl_store_at(A.R, A.counter[m], A.rows[m], A.cap, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, A.N,
+              m * A.R.n);
+}
+
+// launched behind the store, after every thread of it has read the old counters: the stream orders it
+__global__ __launch_bounds__(kMaxMembers) void rl_counter_add_many_kernel(const RlStoreMany A) {
+  const int m = threadIdx.x;
+  if (m < A.members) *A.counter[m] += static_cast<uint64_t>(A.R.total);
 }
 
 // ============================================================================ compute_td_loss
@@ -594,23 +625,44 @@ __global__ __launch_bounds__(kBlock) void rl_sync_many_kernel(float* learners, u
 // ---------------------------------------------------------------------------- host side of a call
 // What mg_rainbow_replay_store and the prioritized stores refuse (n == 0 or num_steps == 0 is a no-op the caller
 // returns from before the required arrays are looked at).
-int check_rainbow_store(const char* what, const float* rows, const uint64_t* counter, int64_t capacity,
-                        const mg_transitions* tr, int64_t n, int32_t num_steps) {
-  if (!rows || !counter || !tr) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
-  if (capacity < 1 || capacity > (int64_t{1} << 32))
-    return fail(hipErrorInvalidValue, "%s: need 1 <= capacity <= 2^32", what);
-  if (n < 0 || num_steps < 0) return fail(hipErrorInvalidValue, "%s: n < 0 or num_steps < 0", what);
-  if (tr->goal || tr->next_goal || tr->reward || tr->meta_goal)
-    return fail(hipErrorInvalidValue,
-                "%s: goal, next_goal, reward and meta_goal must be NULL (Rainbow rows have none)", what);
-  if (n == 0 || num_steps == 0) return 0;
-  if (!tr->obs_first || !tr->obs || !(tr->a1 || tr->flags) || !tr->rew)
-    return fail(hipErrorInvalidValue, "%s: obs_first, obs, a1 (or flags) and rew are required", what);
-  if (misaligned(rows, 7) || misaligned(counter, 7) || misaligned(tr->obs_first, 3) || misaligned(tr->obs, 3) ||
-      misaligned(tr->final_obs, 3) || misaligned(tr->rew, 3))
-    return fail(hipErrorInvalidValue, "%s: rows and counter must be 8-byte, the float buffers 4-byte aligned", what);
-  if (n > (static_cast<int64_t>(0x7fffffff) * kBlock) / num_steps)
-    return fail(hipErrorInvalidValue, "%s: n * num_steps exceeds the grid limit", what);
+// The lone stores are the member store's list of one ring: both fill an RlStoreCall and one walk checks it. The
+// member call (`many`) adds the checks of its lists, which come before anything else of a member is looked at.
+struct RlStoreCall {  // in the order of mg_rainbow_replay_store_many's arguments
+  float* const* rows;  // `members` rings and their counters (a lone call: the addresses of its two arguments)
+  uint64_t* const* counter;
+  int32_t members;
+  int64_t capacity;
+  const mg_transitions* tr;
+  int64_t n;  // envs of one member
+  int32_t T;
+};
+
+int check_rainbow_store(const char* what, const RlStoreCall& C, bool many = false) {
+  const auto bad = [what](const char* fmt) { return fail(hipErrorInvalidValue, fmt, what); };
+  if (many && !members_ok(C.members)) return bad("%s: need 1 <= members <= 64");
+  if (!C.rows || !C.counter || !C.tr || (!many && (!C.rows[0] || !C.counter[0]))) return bad("%s: NULL pointer");
+  for (int m = 0; many && m < C.members; ++m) {
+    if (!C.rows[m] || !C.counter[m]) return bad("%s: NULL pointer (a member's rows or counter)");
+    if (misaligned(C.rows[m], 7) || misaligned(C.counter[m], 7))
+      return bad("%s: every member's rows and counter must be 8-byte aligned");
+    for (int k = 0; k < m; ++k)
+      if (C.rows[k] == C.rows[m] || C.counter[k] == C.counter[m])
+        return bad("%s: a ring is listed twice (two members' appends to one ring have no defined order)");
+  }
+  if (C.capacity < 1 || C.capacity > (int64_t{1} << 32)) return bad("%s: need 1 <= capacity <= 2^32");
+  if (C.n < 0 || C.T < 0) return bad(many ? "%s: n_member < 0 or num_steps < 0" : "%s: n < 0 or num_steps < 0");
+  const mg_transitions& X = *C.tr;
+  if (X.goal || X.next_goal || X.reward || X.meta_goal)
+    return bad("%s: goal, next_goal, reward and meta_goal must be NULL (Rainbow rows have none)");
+  if (C.n == 0 || C.T == 0) return 0;
+  if (!X.obs_first || !X.obs || !(X.a1 || X.flags) || !X.rew)
+    return bad("%s: obs_first, obs, a1 (or flags) and rew are required");
+  if ((!many && (misaligned(C.rows[0], 7) || misaligned(C.counter[0], 7))) || misaligned(X.obs_first, 3) ||
+      misaligned(X.obs, 3) || misaligned(X.final_obs, 3) || misaligned(X.rew, 3))
+    return bad(many ? "%s: the float buffers must be 4-byte aligned"
+                    : "%s: rows and counter must be 8-byte, the float buffers 4-byte aligned");
+  if (C.n > (static_cast<int64_t>(0x7fffffff) * kBlock) / C.T)
+    return bad(many ? "%s: n_member * num_steps exceeds the grid limit" : "%s: n * num_steps exceeds the grid limit");
   return 0;
 }
 
@@ -623,7 +675,7 @@ void rainbow_store(float* rows, uint64_t* counter, int64_t capacity, const mg_tr
   R.n = n;
   R.total = n * num_steps;
   if (host) {
-    for (int64_t i = 0; i < R.total; ++i) rl_store_at(R, counter, rows, capacity, i);
+    for (int64_t i = 0; i < R.total; ++i) rl_store_at(R, counter, rows, capacity, i, n, 0);
     if (tree) host_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha);
     *counter += static_cast<uint64_t>(R.total);
     return;
@@ -631,6 +683,30 @@ void rainbow_store(float* rows, uint64_t* counter, int64_t capacity, const mg_tr
   hipLaunchKernelGGL(rl_store_kernel, dim3(grid_blocks(R.total)), dim3(kBlock), 0, st, R, counter, rows, capacity);
   if (tree) launch_per_store_tree(per_tree(tree, capacity), counter, R.total, alpha, st);
   hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
+}
+
+// The member store after its checks: every member's rows (the member in the grid, or on the host member by member),
+// then every counter moves by T n_member.
+void rainbow_store_many(const RlStoreCall& C, bool host, hipStream_t st) {
+  RlStoreMany A{};
+  A.R.X = *C.tr;
+  A.R.n = C.n;
+  A.R.total = C.n * C.T;
+  A.N = C.n * C.members;
+  A.cap = C.capacity;
+  A.members = C.members;
+  std::copy(C.rows, C.rows + C.members, A.rows);
+  std::copy(C.counter, C.counter + C.members, A.counter);
+  if (host) {
+    for (int m = 0; m < C.members; ++m) {
+      for (int64_t i = 0; i < A.R.total; ++i) rl_store_at(A.R, A.counter[m], A.rows[m], A.cap, i, A.N, m * C.n);
+      *A.counter[m] += static_cast<uint64_t>(A.R.total);
+    }
+    return;
+  }
+  hipLaunchKernelGGL(rl_store_many_kernel, dim3(grid_blocks(A.R.total), static_cast<unsigned>(C.members)),
+                     dim3(kBlock), 0, st, A);
+  hipLaunchKernelGGL(rl_counter_add_many_kernel, dim3(1), dim3(kMaxMembers), 0, st, A);
 }
 
 // One call of mg_rainbow_learn, mg_rainbow_learn_prioritized or a host twin: the arguments as the entry point

@@ -1,9 +1,14 @@
-// mg_rollout_rainbow.h -- Rainbow's acting loop fused with the env step: RbRollout, rainbow_rollout_kernel.
+// mg_rollout_rainbow.h -- Rainbow's acting loop fused with the env step: RbRollout, rainbow_rollout_kernel, the
+// same kernel with the member in the grid (RbRolloutMany, the MANY instances), and the host side the lone and the
+// member entry point share.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
+#include <type_traits>
+
 #include "mg_common.h"
 #include "mg_env.h"
+#include "mg_launch.h"
 #include "mg_rainbow.h"
 #include "mg_stats.h"
 #include "mg_wave_out.h"
@@ -31,24 +36,63 @@ struct RbRollout {
   uint32_t flags;
 };
 
+// ---- the member in the grid (mg_rollout_rainbow_many; the kernel's MANY instances): one batch of members * n_member
+// envs, member m owning envs [m n_member, (m + 1) n_member) and acting with its own packed net. There are no draws,
+// so a member has no seed and no env offset: its net is all the kernel argument carries beside the shared launch.
+struct RbRolloutMany {
+  RbRollout R;                // shared: n = members * n_member, the row stride of every [T, n, ...] output; net unused
+  int64_t n_member;           // a multiple of 64: no wave and no won-mask word spans two members
+  int32_t blocks_per_member;  // ceil(n_member / kRbThreads)
+  int32_t members;
+  const uint8_t* net[kMaxMembers];
+};
+static_assert(sizeof(RbRolloutMany) <= 4096, "HIP's kernel argument limit");
+
+// What a block works on: the shared launch, its first env, where the envs it may touch stop, its net. The lone
+// launch's block b starts at env kRbThreads b and stops at n; with the member in the grid block b is local block
+// b mod blocks_per_member of member b div blocks_per_member and stops at the member's end, all block-uniform.
+__device__ __forceinline__ const RbRollout& rb_launch(const RbRollout& R) { return R; }
+__device__ __forceinline__ const RbRollout& rb_launch(const RbRolloutMany& A) { return A.R; }
+__device__ __forceinline__ int64_t rb_block_base(const RbRollout&) {
+  return static_cast<int64_t>(blockIdx.x) * kRbThreads;
+}
+__device__ __forceinline__ int64_t rb_block_base(const RbRolloutMany& A) {
+  const int m = static_cast<int>(blockIdx.x) / A.blocks_per_member;
+  const int local = static_cast<int>(blockIdx.x) - m * A.blocks_per_member;
+  return m * A.n_member + static_cast<int64_t>(local) * kRbThreads;
+}
+__device__ __forceinline__ int64_t rb_block_end(const RbRollout& R) { return R.n; }
+__device__ __forceinline__ int64_t rb_block_end(const RbRolloutMany& A) {
+  return (static_cast<int>(blockIdx.x) / A.blocks_per_member + 1) * A.n_member;
+}
+__device__ __forceinline__ const uint8_t* rb_block_net(const RbRollout& R) { return R.net; }
+__device__ __forceinline__ const uint8_t* rb_block_net(const RbRolloutMany& A) {
+  return A.net[static_cast<int>(blockIdx.x) / A.blocks_per_member];
+}
+
 // OPP 0: a2 = None, the env's own L0 opponent; OPP 2: the same net on the view rotated by three.
-template <int OPP>
-__global__ __launch_bounds__(kRbThreads) void rainbow_rollout_kernel(const RbRollout R) {
+// MANY: the member in the grid (mg_rollout_rainbow_many) -- the same block on a member's slice of a wider batch:
+// liveness, a wave's rows and its won-mask word end at the member's end, rows stride by the whole batch (R.n).
+template <int OPP, bool MANY = false>
+__global__ __launch_bounds__(kRbThreads) void rainbow_rollout_kernel(
+    const std::conditional_t<MANY, RbRolloutMany, RbRollout> A) {
   static_assert(OPP == 0 || OPP == 2, "opponent modes: 0 (None) and 2 (the same net)");
   __shared__ __attribute__((aligned(16))) uint8_t lds_net[kRbNetBytes];
   __shared__ __attribute__((aligned(16))) float tile[kRbThreads * kObs];
+  const RbRollout& R = rb_launch(A);
   const mg_params& P = R.P;
   const int tid = threadIdx.x;
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kRbThreads;
+  const int64_t base = rb_block_base(A);
+  const int64_t end = rb_block_end(A);
   const int64_t i = base + tid;
-  const bool live = i < R.n;
+  const bool live = i < end;
   const int64_t wbase = base + (tid & ~63);
-  const int64_t wrem = R.n - wbase;
+  const int64_t wrem = end - wbase;
   const int wrows = wrem <= 0 ? 0 : (wrem < 64 ? static_cast<int>(wrem) : 64);
   const bool autoreset = (R.flags & MG_AUTORESET) != 0;
   float* wtile = tile + (tid & ~63) * kObs;
 
-  rainbow_to_lds(R.net, lds_net);
+  rainbow_to_lds(rb_block_net(A), lds_net);
   Env e;
   EpStats sreg;
   {  // the observation the first step acts on, into the env's tile row (zeros past n)
@@ -95,6 +139,39 @@ __global__ __launch_bounds__(kRbThreads) void rainbow_rollout_kernel(const RbRol
     store_env(R.S, i, e);
     stats_store(R.St, i, sreg);
   }
+}
+
+// ============================================================================ the host side of a call
+// What mg_rollout_rainbow and mg_rollout_rainbow_many share: the check of num_steps and the mode (the member call's
+// texts carry its name in front), the fill of the launch, the instance.
+int check_rb_rollout_steps_mode(bool many, int32_t num_steps, int32_t opponent_mode) {
+  if (num_steps < 0 || num_steps > 65535)
+    return fail(hipErrorInvalidValue, many ? "mg_rollout_rainbow_many: %s" : "%s",
+                "need 0 <= num_steps <= 65535 (split longer rollouts)");
+  if (opponent_mode != 0 && opponent_mode != 2)
+    return fail(hipErrorInvalidValue, many ? "mg_rollout_rainbow_many: %s" : "mg_rollout_rainbow: %s",
+                "opponent_mode must be 0 (None) or 2 (the same net on state[3:] + state[:3])");
+  return 0;
+}
+
+RbRollout make_rb_rollout(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                          int64_t n, int32_t num_steps, uint32_t flags) {
+  RbRollout R{};
+  R.P = *params;
+  R.R0 = reset0(*params);
+  R.S = *state;
+  R.T = *traj;
+  if (stats) R.St = *stats;
+  R.n = n;
+  R.num_steps = num_steps;
+  R.flags = flags;
+  return R;
+}
+
+// They come out in the code object in the order of first naming: the lone call's.
+template <bool MANY>
+auto rainbow_rollout_instance(int32_t opponent_mode) -> void (*)(std::conditional_t<MANY, RbRolloutMany, RbRollout>) {
+  return opponent_mode == 0 ? rainbow_rollout_kernel<0, MANY> : rainbow_rollout_kernel<2, MANY>;
 }
 
 }  // namespace

@@ -33,7 +33,7 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
 
         return RainbowNet
     if name in ("RainbowReplay", "RainbowLearner", "PrioritizedRainbowReplay", "PrioritizedRainbowLearner",
-                "DeviceNoise"):
+                "DeviceNoise", "store_rainbow_rollout_many"):
         from . import rainbow_learn
 
         return getattr(rainbow_learn, name)

@@ -280,6 +280,15 @@ def _load(path=LIB_PATH):
     for f in (lib.mg_rainbow_learn_many_init, lib.mg_rainbow_learn_many, lib.mg_host_rainbow_learn_many,
               lib.mg_rainbow_noise_many, lib.mg_host_rainbow_noise_many, lib.mg_rainbow_sync_target_many):
         f.restype = _c.c_int
+    # a Rainbow population acting (additive to ABI 21): the members' rollouts in one launch, their stores in two
+    lib.mg_rollout_rainbow_many.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _c.c_int32,
+                                            _c.POINTER(_P), _c.c_int32, _c.c_uint32, _P]
+    rl_store_many = [_c.POINTER(_P), _c.POINTER(_P), _c.c_int32, _c.c_int64, _c.POINTER(Transitions), _c.c_int64,
+                     _c.c_int32]
+    lib.mg_rainbow_replay_store_many.argtypes = rl_store_many + [_P]
+    lib.mg_host_rainbow_replay_store_many.argtypes = rl_store_many
+    for f in (lib.mg_rollout_rainbow_many, lib.mg_rainbow_replay_store_many, lib.mg_host_rainbow_replay_store_many):
+        f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,
               lib.mg_rollout_hdqn, lib.mg_replay_store, lib.mg_replay_sample, lib.mg_goal_status,

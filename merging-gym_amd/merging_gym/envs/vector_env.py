@@ -451,6 +451,33 @@ class MergeVecEnv:
         nat.check(rc, "mg_rollout_rainbow")
         return buf["_result"]
 
+    def rollout_rainbow_many(self, num_steps: int, nets, opponent: str = "self", final_observation: bool = True,
+                             won_mask: bool = True):
+        """rollout_rainbow for M actors in ONE launch: nets is a list of M RainbowNets, and member m owns envs
+        [m n, (m + 1) n), n = num_envs / M (a multiple of 64: a won-mask word never spans two members), where it
+        acts with nets[m]. opponent: "self" or "none" for every member (cross-play is not offered: two Rainbow
+        nets and the observation tile exceed one CU's LDS). There is no draw, so member m's slice is bit for bit
+        what a lone MergeVecEnv(n) holding the slice's state gives for rollout_rainbow(num_steps, nets[m],
+        opponent). Returns the same [T, N, ...] dict as rollout_rainbow (rainbow_learn.store_rainbow_rollout_many
+        appends it to M replays in place). The nets' addresses travel in the kernel argument: a call allocates
+        and synchronises nothing."""
+        nat = self._nat
+        nets = list(nets)
+        M = len(nets)
+        if not 1 <= M <= MAX_MEMBERS:
+            raise ValueError(f"rollout_rainbow_many takes 1..{MAX_MEMBERS} nets, got {M}")
+        if self.num_envs % M or (self.num_envs // M) % 64:
+            raise ValueError(f"num_envs = {self.num_envs} must be {M} slices of a multiple of 64 envs (a won-mask "
+                             "word covers 64 envs, so two members must not share one)")
+        T = int(num_steps)
+        mode = {"none": 0, "self": 2}[opponent]
+        buf = self._traj(T, final_observation, won_mask)
+        packed = (ctypes.c_void_p * M)(*(net.packed.data_ptr() for net in nets))
+        rc = nat.lib.mg_rollout_rainbow_many(self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref,
+                                             self.num_envs // M, M, T, packed, mode, self._flags, self._stream())
+        nat.check(rc, "mg_rollout_rainbow_many")
+        return buf["_result"]
+
     def rollout_hdqn(self, num_steps: int, meta, lower, seed: int, opponent="none",
                      episilo: float = 0.7, first_step=None, final_observation: bool = True,
                      won_mask: bool = False, ring=None, goal_memory: bool = False):

@@ -42,7 +42,7 @@ from __future__ import annotations
 
 import ctypes
 
-from ._base import LearnerBase, RingBase
+from ._base import MAX_MEMBERS, LearnerBase, RingBase
 from ._device import U64, ptr
 from .rainbow import NOISY, NUM_ATOMS, PLAIN, SHAPES, RainbowNet
 
@@ -222,6 +222,50 @@ class RainbowReplay(RingBase):
         rows = self.sample_rows(batch_size, seed, draw)
         return (rows[:, :_OBS], rows[:, _OBS].to(self._torch.int64), rows[:, _OBS + 1],
                 rows[:, _OBS + 2:2 * _OBS + 2], rows[:, 2 * _OBS + 2])
+
+
+def store_rainbow_rollout_many(replays, obs_first, traj):
+    """Append one rollout of N = M n envs (MergeVecEnv.rollout_rainbow_many's dict; obs_first [N, 10] = the
+    observation before step 0) to M RainbowReplays, member m's slice [m n, (m + 1) n) to replays[m]: exactly what
+    replays[m].store_rollout leaves when given a contiguous copy of the slice, in two launches for all members
+    (mg_rainbow_replay_store_many). The replays are distinct, of one capacity and on one device; a
+    PrioritizedRainbowReplay is refused (its trees need its own store). traj["flags"] is read in place; like
+    store_rollout it needs the rollout's final_observation. Nothing is copied and nothing is synchronised."""
+    from . import _native
+
+    replays = list(replays)
+    M = len(replays)
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"store_rainbow_rollout_many takes 1..{MAX_MEMBERS} replays, got {M}")
+    for r in replays:
+        if isinstance(r, PrioritizedRainbowReplay):
+            raise ValueError("the member store writes rows only: a PrioritizedRainbowReplay's trees need its own "
+                             "store_rollout")
+        if not isinstance(r, RainbowReplay):
+            raise ValueError(f"expected RainbowReplays, got a {type(r).__name__}")
+    r0 = replays[0]
+    torch = r0._torch
+    if any(r.capacity != r0.capacity or r.device != r0.device for r in replays):
+        raise ValueError("the replays share one capacity and one device")
+    if len({id(r) for r in replays}) != M:
+        raise ValueError("a replay is listed twice: two members' appends to one replay have no defined order")
+    final_obs = RingBase._final_observation(traj)
+    flags = traj.get("flags")
+    if (flags is None or flags.dtype != torch.uint8 or flags.dim() != 3 or flags.shape[2] != 4
+            or not flags.is_contiguous() or flags.device != r0.device):
+        raise ValueError(f"the member store reads the rollout's interleaved [T, N, 4] uint8 flags buffer on {r0.device}")
+    T, N = int(flags.shape[0]), int(flags.shape[1])
+    if N % M:
+        raise ValueError(f"N = {N} is not {M} equal slices")
+    obs_first, obs = r0._f32(obs_first, (N, _OBS)), r0._f32(traj["obs"], (T, N, _OBS))
+    rew, final_obs = r0._f32(traj["rew"], (T, N, 2)), r0._f32(final_obs, (T, N, _OBS))
+    tr = _native.Transitions(ptr(obs_first), ptr(obs), ptr(final_obs), None, ptr(rew), None, None, None, None, None,
+                             ptr(flags), None)
+    rows = (ctypes.c_void_p * M)(*(r.memory.data_ptr() for r in replays))
+    counters = (ctypes.c_void_p * M)(*(r._counter.data_ptr() for r in replays))
+    rc = _native.lib.mg_rainbow_replay_store_many(rows, counters, M, r0.capacity, ctypes.byref(tr), N // M, T,
+                                                  r0._stream())
+    _native.check(rc, "mg_rainbow_replay_store_many")
 
 
 class PrioritizedRainbowReplay(RainbowReplay):

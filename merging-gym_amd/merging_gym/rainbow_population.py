@@ -4,22 +4,26 @@ Rainbow's users sweep seeds, lr, gamma and opponents as DQN's do, and one Rainbo
 chain of seven small launches that leaves most of the device idle. A population runs M learners through the
 same seven launches (libmerging_hip.so's mg_rainbow_learn_many), each on its own nets, replay, minibatch seed,
 noise seed, counters and hyperparameters; the noise is always drawn on the device (mg_rainbow_noise_many, one
-launch for all members and updates of a call), so learn() does no host work and no upload:
+launch for all members and updates of a call), so learn() does no host work and no upload. The members act the
+same way: collect() is one observe, one rollout (mg_rollout_rainbow_many, member m on its slice of one env batch
+with its own net) and one store of two launches (mg_rainbow_replay_store_many) for the whole population:
 
     replays = [RainbowReplay(10000, device="cuda:0") for _ in range(8)]
     pop = RainbowPopulation([sd] * 8, replays, lr=[0.001, 0.0005, 0.002] + [0.001] * 5, seed=range(8))
-    envs = [MergeVecEnv(1024, device="cuda:0") for _ in range(8)]
-    for m, env in enumerate(envs):                          # acting is still one rollout and one store per member
-        obs0 = env.observe().clone()
-        replays[m].store_rollout(obs0, env.rollout_rainbow(16, pop.nets[m]))
-    pop.learn(4)                                            # four updates of all eight
+    env = MergeVecEnv(8 * 1024, device="cuda:0")            # member m owns envs [1024 m, 1024 (m + 1))
+    pop.collect(env, 16)                                    # every member acts with its own net and stores
+    pop.learn(4)                                            # into its own replay; four updates of all eight
+    env.member_summaries(8)                                 # each member's episode summary
     pop.sync_target([0, 3])                                 # update_target for members 0 and 3, one launch
     pop.copy_member(best, worst)                            # population-based training's exploit step
 
 Member m is bit for bit the lone RainbowLearner(net, replay, ..., generator=DeviceNoise(noise_seed[m])) built from
-the same net, replay, seeds and hyperparameters: member_state_dict(m) is that learner's state_dict() and loads into
-one, and back. Fused acting for all members (a many-member rollout_rainbow and replay store) is not part of this
-class yet: members act through M rollout_rainbow calls on pop.nets[m], as above.
+the same net, replay, seeds and hyperparameters, acting through rollout_rainbow and store_rollout on a lone env
+that holds its slice: member_state_dict(m) is that learner's state_dict() and loads into one, and back.
+
+Not part of this class: cross-play (a member against another member's net: two Rainbow nets and the observation
+tile exceed one CU's LDS), appending to the replays from inside the rollout kernel, prioritized members, and a
+target sync by episode count (the caller reads env.member_summaries and calls sync_target).
 """
 
 from __future__ import annotations
@@ -158,6 +162,23 @@ class RainbowPopulation:
     @property
     def noise_seed(self):
         return [int(s) for s in self._noise_seeds]
+
+    # ------------------------------------------------------------------ act and store
+    def collect(self, env, num_steps: int, opponent: str = "self"):
+        """The acting half of the loop for every member at once: env.observe(), one
+        env.rollout_rainbow_many(num_steps, self.nets, opponent) -- member m on its slice of env's batch -- and one
+        store_rainbow_rollout_many into self.replays: four launches beside the 4 M of the members in turn, each
+        member's slice, replay and counter bit for bit the lone loop's. Returns the trajectory. Refuses a
+        population whose replays are shared."""
+        from .rainbow_learn import store_rainbow_rollout_many
+
+        if len({id(r) for r in self.replays}) != len(self.replays):
+            raise ValueError("collect() appends each member's transitions to its own ring: this population's "
+                             "rings are shared")
+        obs0 = env.observe()
+        traj = env.rollout_rainbow_many(num_steps, self.nets, opponent)
+        store_rainbow_rollout_many(self.replays, obs0, traj)
+        return traj
 
     # ------------------------------------------------------------------ learn
     def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
