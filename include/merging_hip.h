@@ -1095,6 +1095,65 @@ int mg_host_rainbow_noise_many(const uint64_t* noise_seed, const uint64_t* first
                                int32_t num_updates, float* noise_out);
 int mg_rainbow_sync_target_many(float* learners, int32_t members, uint64_t mask, void* stream);
 
+/* ---- A population of prioritized Rainbow learners (additive to ABI 21) -------------------------------
+ * mg_rainbow_learn_many whose members each draw from a tree of their own: mg_rainbow_learn_prioritized's nine
+ * launches per update -- the sample, mg_rainbow_learn_many's seven, the priority update -- for all members, the
+ * member a grid dimension; nothing is synchronised. The arguments are mg_rainbow_learn_many's, the same table
+ * included, then
+ *
+ *   per         HOST array [members] of mg_per_member: member m's tree buffer (mg_per_bytes(capacity) device
+ *               bytes, 16-byte aligned, as mg_per_init and the stores leave it), the alpha of its priorities, this
+ *               call's beta and its prio_eps; they travel in the kernel argument
+ *   tree_bytes  the bytes of every member's tree buffer
+ *   idx_out [U][M][B] int64, weight_out [U][M][B] fp32: optional (NULL), each update's sampled slots and weights
+ *   scratch     members * mg_rainbow_learn_prioritized_scratch_bytes(batch) bytes, 16-byte aligned
+ *
+ * Contract: for every member m, its learner block, loss, rows, proj, grads, packed net, idx, weights and every
+ * double of its tree (max_priority included) are bit for bit what mg_rainbow_learn_prioritized gives on that
+ * member's buffers, counters, hyperparameters, alpha, beta, prio_eps and slice of the noise. K updates in one call
+ * equal K calls; num_updates == 0 is mg_rainbow_learn_many's. On success the two calls advance every member's
+ * first_update and first_draw by num_updates; a refused call changes nothing.
+ * mg_host_rainbow_learn_prioritized_many is the loop over the members of mg_host_rainbow_learn_prioritized's
+ * update on HOST pointers, synchronously; it needs no table.
+ * Refused before anything is read or launched: what mg_rainbow_learn_many refuses, in its order; then, in
+ * mg_rainbow_learn_prioritized's order, a NULL per, a member's NULL tree, a member's tree not 16-byte aligned;
+ * tree_bytes < mg_per_bytes(capacity); a member's alpha <= 0, beta <= 0 or prio_eps < 0; idx_out not 8-byte or
+ * weight_out not 4-byte aligned; scratch too small; two members that name one tree or one rows buffer (here
+ * learning writes the tree, so a shared replay has no defined order). A refusal of one member's fields names the
+ * member.
+ *
+ * mg_per_store_many: mg_rainbow_replay_store_many into `members` prioritized replays -- member m's slice of one
+ * [T, members * n, ...] batch into rows[m], and into trees[m] what mg_per_store leaves there, with alpha[m]. rows,
+ * counters, trees and alpha are HOST arrays [members]; the capacity and tree_bytes are shared, so every launch
+ * has the lone store's grid, the member beside it: the rows, the leaves, the levels, the single-block tail (a
+ * block per member), then one launch moves every counter by num_steps * n; every launch before it reads the
+ * counters as they were. Contract: member m's rows, counter and tree are bit for bit what mg_per_store leaves when
+ * given a contiguous copy of the slice. Refused: what mg_rainbow_replay_store_many refuses, in its order; then a
+ * NULL trees or alpha, a member's NULL tree, a member's tree not 16-byte aligned, tree_bytes <
+ * mg_per_bytes(capacity), a member's alpha <= 0, a tree listed twice. n == 0 or num_steps == 0 is a no-op.
+ * mg_host_per_store_many: the same on HOST pointers, member by member. */
+typedef struct mg_per_member {
+  void* tree;
+  double alpha, beta, prio_eps;
+} mg_per_member;
+int mg_rainbow_learn_prioritized_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member,
+                                      int32_t members, int64_t capacity, int32_t batch, int32_t num_updates,
+                                      const float* noise, float* loss_out, float* rows_out, float* proj_out,
+                                      float* grads_out, void* packed_out, size_t packed_stride, void* scratch,
+                                      size_t scratch_bytes, const mg_per_member* per, size_t tree_bytes,
+                                      int64_t* idx_out, float* weight_out, void* stream);
+int mg_host_rainbow_learn_prioritized_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                                           int32_t batch, int32_t num_updates, const float* noise, float* loss_out,
+                                           float* rows_out, float* proj_out, float* grads_out, void* scratch,
+                                           size_t scratch_bytes, const mg_per_member* per, size_t tree_bytes,
+                                           int64_t* idx_out, float* weight_out);
+int mg_per_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                      const mg_transitions* tr, int64_t n, int32_t num_steps, void* const* trees, size_t tree_bytes,
+                      const double* alpha, void* stream);
+int mg_host_per_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                           const mg_transitions* tr, int64_t n, int32_t num_steps, void* const* trees,
+                           size_t tree_bytes, const double* alpha);
+
 #ifdef __cplusplus
 }
 #endif

@@ -827,7 +827,8 @@ int mg_per_sample(const void* tree, size_t tree_bytes, const uint64_t* counter, 
     return e;
   const PerSample P{per_tree(const_cast<void*>(tree), capacity), counter, beta, seed, draw, batch, idx_out, nullptr,
                     weight_out, nullptr};
-  hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(batch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), P);
+  hipLaunchKernelGGL(per_sample_kernel<PerSample>, dim3(grid_blocks(batch)), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(stream), P);
   return finish_launch("mg_per_sample");
 }
 
@@ -909,6 +910,55 @@ int mg_host_rainbow_learn_prioritized(float* learner, const float* rows, const u
                alpha, beta, prio_eps, idx_out, weight_out};
   if (int e = check_rainbow_learn("mg_host_rainbow_learn_prioritized", C)) return e;
   return rainbow_learn_host(C);
+}
+
+// ---- a population of prioritized Rainbow learners: mg_rainbow_learn_many with every member's tree ---
+int mg_rainbow_learn_prioritized_many(float* learners, const void* table, size_t table_bytes, mg_dqn_member* member,
+                                      int32_t members, int64_t capacity, int32_t batch, int32_t num_updates,
+                                      const float* noise, float* loss_out, float* rows_out, float* proj_out,
+                                      float* grads_out, void* packed_out, size_t packed_stride, void* scratch,
+                                      size_t scratch_bytes, const mg_per_member* per, size_t tree_bytes,
+                                      int64_t* idx_out, float* weight_out, void* stream) {
+  const RLearnManyCall C{learners, table, table_bytes, member, members, capacity, batch, num_updates, noise,
+                         loss_out, rows_out, proj_out, grads_out, packed_out, packed_stride, scratch, scratch_bytes,
+                         false, true, per, tree_bytes, idx_out, weight_out};
+  if (int e = check_rainbow_learn_many("mg_rainbow_learn_prioritized_many", C)) return e;
+  return rainbow_learn_many_device("mg_rainbow_learn_prioritized_many", C, static_cast<hipStream_t>(stream));
+}
+
+int mg_host_rainbow_learn_prioritized_many(float* learners, mg_dqn_member* member, int32_t members, int64_t capacity,
+                                           int32_t batch, int32_t num_updates, const float* noise, float* loss_out,
+                                           float* rows_out, float* proj_out, float* grads_out, void* scratch,
+                                           size_t scratch_bytes, const mg_per_member* per, size_t tree_bytes,
+                                           int64_t* idx_out, float* weight_out) {
+  const RLearnManyCall C{learners, nullptr, 0, member, members, capacity, batch, num_updates, noise,
+                         loss_out, rows_out, proj_out, grads_out, nullptr, 0, scratch, scratch_bytes,
+                         true, true, per, tree_bytes, idx_out, weight_out};
+  if (int e = check_rainbow_learn_many("mg_host_rainbow_learn_prioritized_many", C)) return e;
+  return rainbow_learn_many_host(C);
+}
+
+int mg_per_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                      const mg_transitions* tr, int64_t n, int32_t num_steps, void* const* trees, size_t tree_bytes,
+                      const double* alpha, void* stream) {
+  const RlStoreCall C{rows, counters, members, capacity, tr, n, num_steps};
+  if (int e = check_rainbow_store("mg_per_store_many", C, true)) return e;
+  if (int e = check_per_store_many("mg_per_store_many", C, trees, tree_bytes, alpha)) return e;
+  if (n == 0 || num_steps == 0) return 0;
+  rainbow_store_many(C, false, static_cast<hipStream_t>(stream), trees, alpha);
+  return finish_launch("mg_per_store_many");
+}
+
+int mg_host_per_store_many(float* const* rows, uint64_t* const* counters, int32_t members, int64_t capacity,
+                           const mg_transitions* tr, int64_t n, int32_t num_steps, void* const* trees,
+                           size_t tree_bytes, const double* alpha) {
+  const RlStoreCall C{rows, counters, members, capacity, tr, n, num_steps};
+  if (int e = check_rainbow_store("mg_host_per_store_many", C, true)) return e;
+  if (int e = check_per_store_many("mg_host_per_store_many", C, trees, tree_bytes, alpha)) return e;
+  g_err[0] = '\0';
+  if (n == 0 || num_steps == 0) return 0;
+  rainbow_store_many(C, true, nullptr, trees, alpha);
+  return 0;
 }
 
 // ---- Rainbow noise on the device (the factors of RainbowDQN.reset_noise, :486-496, :537-541) --------

@@ -1,7 +1,9 @@
 // mg_per.h -- prioritized replay for Rainbow: SumSegmentTree, MinSegmentTree and PrioritizedReplayBuffer
 // (scripts/ranbowdqn.py:130-262, :326-437) as one fp64 tree buffer beside RainbowReplay's rows, with the store,
 // sample and update kernels and the per-element functions the host twins (mg_host_per_*) run too. It stands
-// alone: the learner that samples from the tree is mg_rainbow_learn.h's.
+// alone: the learner that samples from the tree is mg_rainbow_learn.h's. Up to 64 members' trees of one capacity
+// go through the same functions with the member in the grid (PerStoreMany; mg_rainbow_learn.h's PerMany): a
+// member has its own buffer, counter and scalars, nothing else.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -39,6 +41,14 @@ MG_HD PerTree per_tree(void* buf, int64_t capacity) {
   return T;
 }
 MG_HD int64_t per_doubles(int64_t capacity) { return 4 * per_leaves(capacity) + 2; }
+// the tree of `shape`'s capacity in another buffer: the members of a call share C, cap and logC
+MG_HD PerTree per_tree_at(const PerTree& shape, void* buf) {
+  PerTree T = shape;
+  T.sum = static_cast<double*>(buf);
+  T.mn = T.sum + 2 * T.C;
+  T.maxp = T.mn + 2 * T.C;
+  return T;
+}
 
 // element i of the fresh buffer: sums 0.0 (:218), minima +inf (:256), max_priority 1.0 (:351), the pad 0
 MG_HD void per_init_at(const PerTree& T, int64_t i) {
@@ -180,6 +190,40 @@ __global__ __launch_bounds__(kPerTail) void per_tail_kernel(const PerTree T, con
   }
 }
 
+// ---- the member in the grid (mg_per_store_many): the capacity and the store's size are shared, so the count, the
+// levels and every grid are the lone store's; member m = blockIdx.y reads its own counter and writes its own tree.
+struct PerStoreMany {
+  PerTree shape;  // C, cap, logC; the pointers are member 0's and unused
+  int64_t total;
+  void* tree[kMaxMembers];
+  const uint64_t* counter[kMaxMembers];
+  double alpha[kMaxMembers];
+};
+static_assert(sizeof(PerStoreMany) <= 4096, "HIP's kernel argument limit");
+
+__global__ __launch_bounds__(kBlock) void per_fill_many_kernel(const PerStoreMany A) {
+  const int m = blockIdx.y;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  per_fill_at(per_tree_at(A.shape, A.tree[m]), per_segs(*A.counter[m], A.total, A.shape.cap), A.alpha[m], i);
+}
+
+__global__ __launch_bounds__(kBlock) void per_level_many_kernel(const PerStoreMany A, int j) {
+  const int m = blockIdx.y;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  per_level_at(per_tree_at(A.shape, A.tree[m]), per_segs(*A.counter[m], A.total, A.shape.cap), j, i);
+}
+
+// one block per member: the barrier is between a member's level and its own parents
+__global__ __launch_bounds__(kPerTail) void per_tail_many_kernel(const PerStoreMany A, int j0) {
+  const int m = blockIdx.x;
+  const PerTree T = per_tree_at(A.shape, A.tree[m]);
+  const PerSegs G = per_segs(*A.counter[m], A.total, T.cap);
+  for (int j = j0; j <= T.logC; ++j) {
+    per_level_at(T, G, j, threadIdx.x);
+    __syncthreads();
+  }
+}
+
 // The tree's part of a store, after the rows and before the counter moves.
 void launch_per_store_tree(const PerTree& T, const uint64_t* counter, int64_t total, double alpha, hipStream_t st) {
   const int64_t count = per_store_count(total, T.cap);
@@ -190,6 +234,20 @@ void launch_per_store_tree(const PerTree& T, const uint64_t* counter, int64_t to
     hipLaunchKernelGGL(per_level_kernel, dim3(grid_blocks(per_level_items(count, j))), dim3(kBlock), 0, st, T, counter,
                        total, j);
   if (j0 <= T.logC) hipLaunchKernelGGL(per_tail_kernel, dim3(1), dim3(kPerTail), 0, st, T, counter, total, j0);
+}
+
+// launch_per_store_tree for all members: the same launches in the same order, the member in the grid
+void launch_per_store_tree_many(const PerStoreMany& A, int32_t members, hipStream_t st) {
+  const unsigned M = static_cast<unsigned>(members);
+  const PerTree& T = A.shape;
+  const int64_t count = per_store_count(A.total, T.cap);
+  hipLaunchKernelGGL(per_fill_many_kernel, dim3(grid_blocks(count), M), dim3(kBlock), 0, st, A);
+  if (T.logC == 0) return;
+  const int j0 = per_tail_level(count);
+  for (int j = 1; j < j0 && j <= T.logC; ++j)
+    hipLaunchKernelGGL(per_level_many_kernel, dim3(grid_blocks(per_level_items(count, j)), M), dim3(kBlock), 0, st, A,
+                       j);
+  if (j0 <= T.logC) hipLaunchKernelGGL(per_tail_many_kernel, dim3(M), dim3(kPerTail), 0, st, A, j0);
 }
 
 void host_per_store_tree(const PerTree& T, const uint64_t* counter, int64_t total, double alpha) {
@@ -269,7 +327,12 @@ MG_HD void per_sample_at(const PerSample& P, int b) {
   if (P.w_out) P.w_out[b] = w;
 }
 
-__global__ __launch_bounds__(kBlock) void per_sample_kernel(const PerSample P) {
+// One body for the lone sample (Arg = PerSample: blockIdx.y is 0 and unused) and a population's (Arg =
+// mg_rainbow_learn.h's PerMany, from which per_sample_member rebases member blockIdx.y's PerSample).
+MG_HD const PerSample& per_sample_member(const PerSample& P, int) { return P; }
+template <class Arg>
+__global__ __launch_bounds__(kBlock) void per_sample_kernel(const Arg Q) {
+  const PerSample& P = per_sample_member(Q, blockIdx.y);
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b < P.B) per_sample_at(P, b);
 }
@@ -300,7 +363,9 @@ MG_HD void per_update_leaf_at(const PerUpdate& U, int b) {
 
 // One block, one thread per entry: the last of the entries that name a slot sets its leaf (the reference's
 // loop order, :431-435), max_priority takes every entry's priority, then each path is rebuilt a level at a time.
-__global__ __launch_bounds__(kPerTail) void per_update_kernel(const PerUpdate U) {
+// per_update_kernel runs it as its one block; a population's (mg_rainbow_learn.h's per_update_many_kernel) as one
+// block per member, each on its own tree, so the barriers order a member's own levels.
+__device__ __forceinline__ void per_update_block(const PerUpdate& U) {
   __shared__ int64_t sidx[kPerTail];
   __shared__ float smax[kPerTail];
   const int b = threadIdx.x;
@@ -322,6 +387,8 @@ __global__ __launch_bounds__(kPerTail) void per_update_kernel(const PerUpdate U)
     __syncthreads();
   }
 }
+
+__global__ __launch_bounds__(kPerTail) void per_update_kernel(const PerUpdate U) { per_update_block(U); }
 
 void host_per_update(const PerUpdate& U) {
   const int64_t len = per_len(U.counter, U.T.cap);

@@ -4,7 +4,9 @@
 // one (mg_per.h's tree, sample and update) without a tree, so a call has one check, one launch order beside
 // its host twin and one pair of drivers; the replay stores likewise. A population of up to 64 plain learners
 // (mg_rainbow_learn_many) runs the same kernel bodies with the member in the grid: each kernel is a template on
-// its argument, RLearn for the lone call or RLearnMany, from which rl_member rebases member m's RLearn.
+// its argument, RLearn for the lone call or RLearnMany, from which rl_member rebases member m's RLearn. The members
+// may be prioritized too (mg_rainbow_learn_prioritized_many): PerMany carries their trees to mg_per.h's sample and
+// update kernels, templated the same way, and mg_per_store_many is the member store with the trees' launches.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -430,10 +432,11 @@ struct RLearnMany {
   const LearnMember* table;  // [members]
   const float* noise;        // this update's factors [members][2][kRlFactors]
   float *rows_out, *loss_out, *proj_out, *grads_out;  // this update's [members, ...], or NULL
-  int64_t stride;            // floats of one member's scratch: rl_scratch(B, false).total
+  int64_t stride;            // floats of one member's scratch: rl_scratch(B, prioritized).total
   int64_t cap;
   int32_t B, members;
   float inv_b;
+  int32_t prioritized;       // the members' rows and weights are their scratch's pidx and pw (PerMany's sample)
   uint64_t draw[kMaxMembers];
   float step[kMaxMembers];
   float bc2s[kMaxMembers];
@@ -454,7 +457,10 @@ MG_HD RLearn rl_member(const RLearnMany& Q, int m) {
   RLearn L{};
   L.buf = Q.learners + static_cast<int64_t>(m) * kRlLearner;
   L.ring = T.ring, L.counter = T.counter, L.cap = Q.cap, L.seed = T.seed, L.draw = Q.draw[m], L.B = Q.B;
-  rl_set_scratch(L, Q.scratch + m * Q.stride, rl_scratch(Q.B, false));
+  const RlScratch S = rl_scratch(Q.B, Q.prioritized != 0);
+  float* s = Q.scratch + m * Q.stride;
+  rl_set_scratch(L, s, S);
+  if (Q.prioritized) L.pidx = reinterpret_cast<const int64_t*>(s + S.pidx), L.pw = s + S.pw;
   L.noise = Q.noise ? Q.noise + static_cast<int64_t>(m) * 2 * kRlFactors : nullptr;  // NULL in front of the updates
   L.rows_out = Q.rows_out ? Q.rows_out + static_cast<int64_t>(m) * Q.B * kRlRow : nullptr;
   L.loss_out = Q.loss_out ? Q.loss_out + m : nullptr;
@@ -465,6 +471,48 @@ MG_HD RLearn rl_member(const RLearnMany& Q, int m) {
   return L;
 }
 MG_HD const RLearn& rl_member(const RLearn& L, int) { return L; }
+
+// A population of prioritized learners (mg_rainbow_learn_prioritized_many): what the sample in front of an update
+// and the priority update behind it read, for all members (mg_per.h's sample kernel, templated as the learner's
+// are, and its update block).
+// A member's idx [B], w [B] and the loss_b its update reads are its slice of the learners' scratch; its counter
+// and seed are its entry of the learners' table; its tree, alpha, beta, prio_eps and draw travel by value.
+struct PerMany {
+  PerTree shape;   // C, cap, logC, shared; the pointers are unused
+  float* scratch;  // [members, stride]
+  const LearnMember* table;
+  int64_t stride, pidx, pw, lossb;  // floats: RLearnMany's stride, rl_scratch's sections
+  int64_t* idx_out;                 // this update's [members, B], or NULL
+  float* w_out;
+  int32_t B;
+  void* tree[kMaxMembers];
+  double alpha[kMaxMembers], beta[kMaxMembers];
+  uint64_t draw[kMaxMembers];
+  float add[kMaxMembers];  // prio_eps, rounded as the lone call rounds it
+};
+static_assert(sizeof(PerMany) <= 2560, "the by-value kernel argument stays inside HIP's 4096 bytes");
+
+MG_HD PerSample per_sample_member(const PerMany& Q, int m) {
+  const LearnMember& T = Q.table[m];
+  float* s = Q.scratch + m * Q.stride;
+  PerSample P;
+  P.T = per_tree_at(Q.shape, Q.tree[m]);
+  P.counter = T.counter, P.beta = Q.beta[m], P.seed = T.seed, P.draw = Q.draw[m], P.B = Q.B;
+  P.idx = reinterpret_cast<int64_t*>(s + Q.pidx), P.w = s + Q.pw;
+  P.idx_out = Q.idx_out ? Q.idx_out + static_cast<int64_t>(m) * Q.B : nullptr;
+  P.w_out = Q.w_out ? Q.w_out + static_cast<int64_t>(m) * Q.B : nullptr;
+  return P;
+}
+MG_HD PerUpdate per_update_member(const PerMany& Q, int m) {
+  const float* s = Q.scratch + m * Q.stride;
+  return PerUpdate{per_tree_at(Q.shape, Q.tree[m]), Q.table[m].counter, Q.alpha[m],
+                   reinterpret_cast<const int64_t*>(s + Q.pidx), s + Q.lossb, Q.add[m], 1, Q.B};
+}
+
+// per_update_kernel's block for every member: block m on member m's tree
+__global__ __launch_bounds__(kPerTail) void per_update_many_kernel(const PerMany Q) {
+  per_update_block(per_update_member(Q, blockIdx.x));
+}
 
 // What the two noisy backward launches read: the lone call's layers as the host built them, or member m's
 // built where they are used.
@@ -685,9 +733,31 @@ void rainbow_store(float* rows, uint64_t* counter, int64_t capacity, const mg_tr
   hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, st, counter, static_cast<uint64_t>(R.total));
 }
 
+// What mg_per_store_many refuses of its trees, behind check_rainbow_store's walk of the rings.
+int check_per_store_many(const char* what, const RlStoreCall& C, void* const* trees, size_t tree_bytes,
+                         const double* alpha) {
+  if (!trees || !alpha) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  for (int m = 0; m < C.members; ++m)
+    if (!trees[m]) return fail_member(what, m, "NULL pointer (tree)");
+  for (int m = 0; m < C.members; ++m)
+    if (misaligned(trees[m], 15)) return fail_member(what, m, "the tree buffer must be 16-byte aligned");
+  if (tree_bytes < static_cast<size_t>(per_doubles(C.capacity)) * sizeof(double))
+    return fail(hipErrorInvalidValue, "%s: tree buffer smaller than mg_per_bytes(capacity)", what);
+  for (int m = 0; m < C.members; ++m)
+    if (!(alpha[m] > 0.0)) return fail_member(what, m, "need alpha > 0");
+  for (int m = 0; m < C.members; ++m)
+    for (int k = 0; k < m; ++k)
+      if (trees[k] == trees[m])
+        return fail_member(what, m,
+                           "its tree is another member's (two members' stores to one tree have no defined order)");
+  return 0;
+}
+
 // The member store after its checks: every member's rows (the member in the grid, or on the host member by member),
-// then every counter moves by T n_member.
-void rainbow_store_many(const RlStoreCall& C, bool host, hipStream_t st) {
+// with trees the trees' part (launch_per_store_tree's launches, which read the counters before they move), then
+// every counter moves by T n_member.
+void rainbow_store_many(const RlStoreCall& C, bool host, hipStream_t st, void* const* trees = nullptr,
+                        const double* alpha = nullptr) {
   RlStoreMany A{};
   A.R.X = *C.tr;
   A.R.n = C.n;
@@ -700,12 +770,22 @@ void rainbow_store_many(const RlStoreCall& C, bool host, hipStream_t st) {
   if (host) {
     for (int m = 0; m < C.members; ++m) {
       for (int64_t i = 0; i < A.R.total; ++i) rl_store_at(A.R, A.counter[m], A.rows[m], A.cap, i, A.N, m * C.n);
+      if (trees) host_per_store_tree(per_tree(trees[m], A.cap), A.counter[m], A.R.total, alpha[m]);
       *A.counter[m] += static_cast<uint64_t>(A.R.total);
     }
     return;
   }
   hipLaunchKernelGGL(rl_store_many_kernel, dim3(grid_blocks(A.R.total), static_cast<unsigned>(C.members)),
                      dim3(kBlock), 0, st, A);
+  if (trees) {
+    PerStoreMany P{};
+    P.shape = per_tree(trees[0], A.cap);
+    P.total = A.R.total;
+    std::copy(trees, trees + C.members, P.tree);
+    std::copy(A.counter, A.counter + C.members, P.counter);
+    std::copy(alpha, alpha + C.members, P.alpha);
+    launch_per_store_tree_many(P, C.members, st);
+  }
   hipLaunchKernelGGL(rl_counter_add_many_kernel, dim3(1), dim3(kMaxMembers), 0, st, A);
 }
 
@@ -804,7 +884,7 @@ void rainbow_learn_set_update(RLearnCall& C, int32_t u) {
 // seven leaves the next update's effective weights.
 void launch_rainbow_learn_update(const RLearnCall& C, hipStream_t st) {
   const RLearn& L = C.L;
-  if (C.prioritized) hipLaunchKernelGGL(per_sample_kernel, dim3(grid_blocks(L.B)), dim3(kBlock), 0, st, C.P);
+  if (C.prioritized) hipLaunchKernelGGL(per_sample_kernel<PerSample>, dim3(grid_blocks(L.B)), dim3(kBlock), 0, st, C.P);
   hipLaunchKernelGGL(rl_forward_kernel<RLearn>, dim3(L.B), dim3(2 * kRlThreads), 0, st, L);
   const RlHeads H{rl_bwd_layer(L, 0), rl_bwd_layer(L, 1)};
   const RlStreams S{L, rl_bwd_layer(L, 2), rl_bwd_layer(L, 3)};
@@ -936,7 +1016,43 @@ struct RLearnManyCall {
   void* scratch;
   size_t scratch_bytes;
   bool host;
+  // mg_rainbow_learn_prioritized_many and its twin (else zero): every member's tree and exponents, the optional
+  // outputs [U][M][B]
+  bool prioritized;
+  const mg_per_member* per;
+  size_t tree_bytes;
+  int64_t* idx_out;
+  float* weight_out;
 };
+
+// What the prioritized population's calls refuse behind check_rainbow_learn_many's checks: check_rainbow_learn's
+// prioritized part in its order, a member's named, then the replays two members share.
+int check_rainbow_learn_many_per(const char* what, const RLearnManyCall& C) {
+  if (!C.per) return fail(hipErrorInvalidValue, "%s: NULL pointer", what);
+  for (int m = 0; m < C.members; ++m)
+    if (!C.per[m].tree) return fail_member(what, m, "NULL pointer (tree)");
+  for (int m = 0; m < C.members; ++m)
+    if (misaligned(C.per[m].tree, 15)) return fail_member(what, m, "the tree buffer must be 16-byte aligned");
+  if (C.tree_bytes < static_cast<size_t>(per_doubles(C.capacity)) * sizeof(double))
+    return fail(hipErrorInvalidValue, "%s: tree buffer smaller than mg_per_bytes(capacity)", what);
+  for (int m = 0; m < C.members; ++m) {
+    if (!(C.per[m].alpha > 0.0)) return fail_member(what, m, "need alpha > 0");
+    if (!(C.per[m].beta > 0.0)) return fail_member(what, m, "need beta > 0");
+    if (!(C.per[m].prio_eps >= 0.0)) return fail_member(what, m, "need prio_eps >= 0");
+  }
+  if (misaligned(C.idx_out, 7) || misaligned(C.weight_out, 3))
+    return fail(hipErrorInvalidValue, "%s: idx_out must be 8-byte, weight_out 4-byte aligned", what);
+  const size_t one = static_cast<size_t>(rl_scratch(C.batch, true).total) * sizeof(float);
+  if (C.scratch_bytes < one * static_cast<size_t>(C.members))
+    return fail(hipErrorInvalidValue,
+                "%s: scratch smaller than members * mg_rainbow_learn_prioritized_scratch_bytes(batch)", what);
+  for (int m = 0; m < C.members; ++m)
+    for (int k = 0; k < m; ++k)
+      if (C.per[k].tree == C.per[m].tree || C.member[k].rows == C.member[m].rows)
+        return fail_member(what, m, "its tree or rows are another member's (learning writes the tree: a shared "
+                                    "replay has no defined order)");
+  return 0;
+}
 
 // What the two refuse, before anything is read or launched: check_rainbow_learn's checks in its order, the
 // members' behind the call's at each step.
@@ -960,18 +1076,43 @@ int check_rainbow_learn_many(const char* what, const RLearnManyCall& C) {
   const size_t one = static_cast<size_t>(rl_scratch(C.batch, false).total) * sizeof(float);
   if (C.scratch_bytes < one * static_cast<size_t>(C.members))
     return fail(hipErrorInvalidValue, "%s: scratch smaller than members * mg_rainbow_learn_scratch_bytes(batch)", what);
-  if (C.host) return 0;
-  return check_rainbow_member_table(what, C.table, C.table_bytes, C.members);
+  if (!C.host)
+    if (int e = check_rainbow_member_table(what, C.table, C.table_bytes, C.members)) return e;
+  return C.prioritized ? check_rainbow_learn_many_per(what, C) : 0;
 }
 
 // The fields of RLearnMany that do not change from one update of a call to the next.
 RLearnMany make_rainbow_learn_many(const RLearnManyCall& C, const LearnMember* table) {
   RLearnMany Q{};
   Q.learners = C.learners, Q.scratch = static_cast<float*>(C.scratch), Q.table = table;
-  Q.stride = rl_scratch(C.batch, false).total;
+  Q.stride = rl_scratch(C.batch, C.prioritized).total;
   Q.cap = C.capacity, Q.B = C.batch, Q.members = C.members;
   Q.inv_b = static_cast<float>(1.0 / C.batch);
+  Q.prioritized = C.prioritized ? 1 : 0;
   return Q;
+}
+
+// The same of PerMany, for a prioritized call: make_rainbow_learn's P and U for every member.
+PerMany make_per_many(const RLearnManyCall& C, const RLearnMany& Q) {
+  const RlScratch S = rl_scratch(C.batch, true);
+  PerMany P{};
+  P.shape = per_tree(C.per[0].tree, C.capacity);
+  P.scratch = Q.scratch, P.table = Q.table, P.stride = Q.stride;
+  P.pidx = S.pidx, P.pw = S.pw, P.lossb = S.lossb, P.B = C.batch;
+  for (int m = 0; m < C.members; ++m) {
+    P.tree[m] = C.per[m].tree, P.alpha[m] = C.per[m].alpha, P.beta[m] = C.per[m].beta;
+    P.add[m] = static_cast<float>(C.per[m].prio_eps);
+  }
+  return P;
+}
+
+// Update number u of a prioritized call: the members' draws as RLearnMany carries them, the update's rows of
+// idx_out and weight_out.
+void per_many_set_update(PerMany& P, const RLearnManyCall& C, const RLearnMany& Q, int32_t u) {
+  std::copy(Q.draw, Q.draw + Q.members, P.draw);
+  const int64_t umb = static_cast<int64_t>(u) * Q.members * Q.B;
+  P.idx_out = C.idx_out ? C.idx_out + umb : nullptr;
+  P.w_out = C.weight_out ? C.weight_out + umb : nullptr;
 }
 
 // Update number u of a call: every member's draw and Adam's step t + 1 (t = its first_update + u) from the
@@ -1011,15 +1152,23 @@ void launch_rainbow_learn_many_update(const RLearnMany& Q, hipStream_t st) {
   hipLaunchKernelGGL(rl_noise_eff_kernel<RLearnMany>, dim3(grid_blocks(2 * kRlEps), M), dim3(kBlock), 0, st, Q, 1);
 }
 
-// mg_rainbow_learn_many after its check: rainbow_learn_device's order for all members at once -- the effective
-// weights of the stored noise, the updates, the pack -- so num_updates == 0 still packs.
+// mg_rainbow_learn_many or mg_rainbow_learn_prioritized_many after its check: rainbow_learn_device's order for all
+// members at once -- the effective weights of the stored noise, the updates, the pack -- so num_updates == 0
+// still packs.
 int rainbow_learn_many_device(const char* what, const RLearnManyCall& C, hipStream_t st) {
   RLearnMany Q = make_rainbow_learn_many(C, static_cast<const LearnMember*>(C.table));
   const unsigned M = static_cast<unsigned>(Q.members);
   hipLaunchKernelGGL(rl_noise_eff_kernel<RLearnMany>, dim3(grid_blocks(2 * kRlEps), M), dim3(kBlock), 0, st, Q, 0);
+  PerMany P{};
+  if (C.prioritized) P = make_per_many(C, Q);
   for (int32_t u = 0; u < C.num_updates; ++u) {
     rainbow_learn_many_set_update(Q, C, u);
+    if (C.prioritized) {  // launch_rainbow_learn_update's nine: the members' samples in front, their priorities behind
+      per_many_set_update(P, C, Q, u);
+      hipLaunchKernelGGL(per_sample_kernel<PerMany>, dim3(grid_blocks(Q.B), M), dim3(kBlock), 0, st, P);
+    }
     launch_rainbow_learn_many_update(Q, st);
+    if (C.prioritized) hipLaunchKernelGGL(per_update_many_kernel, dim3(M), dim3(kPerTail), 0, st, P);
   }
   if (C.packed_out)
     hipLaunchKernelGGL(rainbow_pack_many_kernel, dim3(grid_blocks(kRbNetBytes / 4), M), dim3(kBlock), 0, st, Q.learners,
@@ -1030,8 +1179,8 @@ int rainbow_learn_many_device(const char* what, const RLearnManyCall& C, hipStre
   return 0;
 }
 
-// mg_host_rainbow_learn_many after its check: host_rl_update member by member, each on the RLearn the kernels
-// rebase, from a table on the stack.
+// mg_host_rainbow_learn_many or mg_host_rainbow_learn_prioritized_many after its check: host_rl_update member by
+// member, each on the RLearn the kernels rebase, from a table on the stack.
 int rainbow_learn_many_host(const RLearnManyCall& C) {
   LearnMember table[kMaxMembers];
   for (int m = 0; m < C.members; ++m) table[m] = learn_member_entry(C.member[m]);
@@ -1040,9 +1189,19 @@ int rainbow_learn_many_host(const RLearnManyCall& C) {
     const RLearn L = rl_member(Q, m);
     for (int i = 0; i < 2 * kRlEps; ++i) rl_noise_eff_at(L, i, false);
   }
+  PerMany P{};
+  if (C.prioritized) P = make_per_many(C, Q);
   for (int32_t u = 0; u < C.num_updates; ++u) {
     rainbow_learn_many_set_update(Q, C, u);
-    for (int m = 0; m < Q.members; ++m) host_rl_update(rl_member(Q, m));
+    if (C.prioritized) per_many_set_update(P, C, Q, u);
+    for (int m = 0; m < Q.members; ++m) {  // host_rainbow_learn_update, member by member
+      if (C.prioritized) {
+        const PerSample S = per_sample_member(P, m);
+        for (int b = 0; b < Q.B; ++b) per_sample_at(S, b);
+      }
+      host_rl_update(rl_member(Q, m));
+      if (C.prioritized) host_per_update(per_update_member(P, m));
+    }
   }
   learn_advance(C.member, C.members, C.num_updates);
   g_err[0] = '\0';

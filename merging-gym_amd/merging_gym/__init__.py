@@ -24,16 +24,16 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from .population import DQNPopulation
 
         return DQNPopulation
-    if name == "RainbowPopulation":
-        from .rainbow_population import RainbowPopulation
+    if name in ("RainbowPopulation", "PrioritizedRainbowPopulation"):
+        from . import rainbow_population
 
-        return RainbowPopulation
+        return getattr(rainbow_population, name)
     if name == "RainbowNet":
         from .rainbow import RainbowNet
 
         return RainbowNet
     if name in ("RainbowReplay", "RainbowLearner", "PrioritizedRainbowReplay", "PrioritizedRainbowLearner",
-                "DeviceNoise", "store_rainbow_rollout_many"):
+                "DeviceNoise", "store_rainbow_rollout_many", "store_prioritized_rollout_many"):
         from . import rainbow_learn
 
         return getattr(rainbow_learn, name)

@@ -80,6 +80,12 @@ class DqnMember(_c.Structure):
                 ("first_draw", _c.c_uint64), ("hyper", DqnHyper)]
 
 
+class PerMember(_c.Structure):
+    """struct mg_per_member: what one member of mg_rainbow_learn_prioritized_many adds to its mg_dqn_member -- its
+    tree buffer, the alpha of its priorities, the call's beta and its prio_eps."""
+    _fields_ = [("tree", _P), ("alpha", _c.c_double), ("beta", _c.c_double), ("prio_eps", _c.c_double)]
+
+
 class QnetActor(_c.Structure):
     """struct mg_qnet_actor: one member of mg_rollout_qnet_many -- its packed net, its opponent's (mode 3), its
     seed and its two greedy thresholds."""
@@ -288,6 +294,18 @@ def _load(path=LIB_PATH):
     lib.mg_rainbow_replay_store_many.argtypes = rl_store_many + [_P]
     lib.mg_host_rainbow_replay_store_many.argtypes = rl_store_many
     for f in (lib.mg_rollout_rainbow_many, lib.mg_rainbow_replay_store_many, lib.mg_host_rainbow_replay_store_many):
+        f.restype = _c.c_int
+    # a population of prioritized Rainbow learners (additive to ABI 21): learn with every member's tree, the store
+    PM = _c.POINTER(PerMember)
+    per_many = [PM, _c.c_size_t, _P, _P]
+    lib.mg_rainbow_learn_prioritized_many.argtypes = ([_P, _P, _c.c_size_t] + rl_many
+                                                      + [_P, _c.c_size_t, _P, _c.c_size_t] + per_many + [_P])
+    lib.mg_host_rainbow_learn_prioritized_many.argtypes = [_P] + rl_many + [_P, _c.c_size_t] + per_many
+    per_store_many = rl_store_many + [_c.POINTER(_P), _c.c_size_t, _c.POINTER(_c.c_double)]
+    lib.mg_per_store_many.argtypes = per_store_many + [_P]
+    lib.mg_host_per_store_many.argtypes = per_store_many
+    for f in (lib.mg_rainbow_learn_prioritized_many, lib.mg_host_rainbow_learn_prioritized_many,
+              lib.mg_per_store_many, lib.mg_host_per_store_many):
         f.restype = _c.c_int
     for f in (lib.mg_step, lib.mg_step_random, lib.mg_reset, lib.mg_observe, lib.mg_rollout_random,
               lib.mg_time_next_launch, lib.mg_qnet_pack, lib.mg_qnet_forward, lib.mg_rollout_qnet,

@@ -229,20 +229,34 @@ def store_rainbow_rollout_many(replays, obs_first, traj):
     observation before step 0) to M RainbowReplays, member m's slice [m n, (m + 1) n) to replays[m]: exactly what
     replays[m].store_rollout leaves when given a contiguous copy of the slice, in two launches for all members
     (mg_rainbow_replay_store_many). The replays are distinct, of one capacity and on one device; a
-    PrioritizedRainbowReplay is refused (its trees need its own store). traj["flags"] is read in place; like
-    store_rollout it needs the rollout's final_observation. Nothing is copied and nothing is synchronised."""
+    PrioritizedRainbowReplay is refused (its trees need store_prioritized_rollout_many). traj["flags"] is read in
+    place; like store_rollout it needs the rollout's final_observation. Nothing is copied and nothing is
+    synchronised."""
+    _store_rollout_many("store_rainbow_rollout_many", list(replays), obs_first, traj, False)
+
+
+def store_prioritized_rollout_many(replays, obs_first, traj):
+    """store_rainbow_rollout_many for M PrioritizedRainbowReplays (mg_per_store_many): member m's rows, counter and
+    trees are exactly what replays[m].store_rollout leaves when given a contiguous copy of its slice -- every stored
+    transition enters with that replay's max_priority ** alpha. The trees' launches are the lone store's with the
+    member in the grid, between the rows' launch and the counters'. The replays are distinct, of one capacity and on
+    one device, each with its own alpha; a plain RainbowReplay is refused."""
+    _store_rollout_many("store_prioritized_rollout_many", list(replays), obs_first, traj, True)
+
+
+def _store_rollout_many(what, replays, obs_first, traj, prioritized):
     from . import _native
 
-    replays = list(replays)
     M = len(replays)
     if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"store_rainbow_rollout_many takes 1..{MAX_MEMBERS} replays, got {M}")
+        raise ValueError(f"{what} takes 1..{MAX_MEMBERS} replays, got {M}")
     for r in replays:
-        if isinstance(r, PrioritizedRainbowReplay):
+        if isinstance(r, PrioritizedRainbowReplay) and not prioritized:
             raise ValueError("the member store writes rows only: a PrioritizedRainbowReplay's trees need its own "
                              "store_rollout")
-        if not isinstance(r, RainbowReplay):
-            raise ValueError(f"expected RainbowReplays, got a {type(r).__name__}")
+        if not isinstance(r, PrioritizedRainbowReplay if prioritized else RainbowReplay):
+            raise ValueError(f"expected {'Prioritized' if prioritized else ''}RainbowReplays, got a "
+                             f"{type(r).__name__}")
     r0 = replays[0]
     torch = r0._torch
     if any(r.capacity != r0.capacity or r.device != r0.device for r in replays):
@@ -263,6 +277,13 @@ def store_rainbow_rollout_many(replays, obs_first, traj):
                              ptr(flags), None)
     rows = (ctypes.c_void_p * M)(*(r.memory.data_ptr() for r in replays))
     counters = (ctypes.c_void_p * M)(*(r._counter.data_ptr() for r in replays))
+    if prioritized:
+        trees = (ctypes.c_void_p * M)(*(r._tree.data_ptr() for r in replays))
+        alphas = (ctypes.c_double * M)(*(r.alpha for r in replays))
+        rc = _native.lib.mg_per_store_many(rows, counters, M, r0.capacity, ctypes.byref(tr), N // M, T, trees,
+                                           r0._tree_bytes, alphas, r0._stream())
+        _native.check(rc, "mg_per_store_many")
+        return
     rc = _native.lib.mg_rainbow_replay_store_many(rows, counters, M, r0.capacity, ctypes.byref(tr), N // M, T,
                                                   r0._stream())
     _native.check(rc, "mg_rainbow_replay_store_many")

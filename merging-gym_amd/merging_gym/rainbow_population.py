@@ -21,9 +21,19 @@ Member m is bit for bit the lone RainbowLearner(net, replay, ..., generator=Devi
 the same net, replay, seeds and hyperparameters, acting through rollout_rainbow and store_rollout on a lone env
 that holds its slice: member_state_dict(m) is that learner's state_dict() and loads into one, and back.
 
-Not part of this class: cross-play (a member against another member's net: two Rainbow nets and the observation
-tile exceed one CU's LDS), appending to the replays from inside the rollout kernel, prioritized members, and a
-target sync by episode count (the caller reads env.member_summaries and calls sync_target).
+PrioritizedRainbowPopulation is the same over M PrioritizedRainbowReplays: every member draws its minibatches from
+its own sum / min trees with its own alpha, beta and prio_eps, nine launches per update of the whole population
+(mg_rainbow_learn_prioritized_many), and collect() stores through mg_per_store_many. Member m is bit for bit the
+lone PrioritizedRainbowLearner(..., generator=DeviceNoise(noise_seed[m])):
+
+    replays = [PrioritizedRainbowReplay(10000, alpha=a, device="cuda:0") for a in (0.4, 0.6, 0.8, 1.0)]
+    pop = PrioritizedRainbowPopulation([sd] * 4, replays, seed=range(4), beta=[0.4, 0.4, 0.6, 0.6])
+    pop.collect(env, 16)
+    pop.learn(4, beta=0.5)                                  # beta per call: one value, or one per member
+
+Not part of these classes: cross-play (a member against another member's net: two Rainbow nets and the observation
+tile exceed one CU's LDS), appending to the replays from inside the rollout kernel, and a target sync by episode
+count (the caller reads env.member_summaries and calls sync_target).
 """
 
 from __future__ import annotations
@@ -35,7 +45,8 @@ from ._base import MAX_MEMBERS, per_member
 from ._device import U64, cuda_device, ptr, raw_stream, require_gpu
 from .rainbow import NUM_ATOMS, RainbowNet
 from .rainbow_learn import (LEARNER_FLOATS, NUM_FACTORS, NUM_PARAMS, ROW, PrioritizedRainbowReplay, RainbowReplay,
-                            _LearnerNet, learner_array, model_state_dict)
+                            _LearnerNet, learner_array, model_state_dict, store_prioritized_rollout_many,
+                            store_rainbow_rollout_many)
 
 
 class _Member:
@@ -68,12 +79,7 @@ class RainbowPopulation:
             raise ValueError(f"a population has 1..{MAX_MEMBERS} members, got {M}")
         if len(replays) != M:
             raise ValueError(f"{M} nets need {M} replays (one replay may appear more than once), got {len(replays)}")
-        for r in replays:
-            if isinstance(r, PrioritizedRainbowReplay):
-                raise ValueError("a RainbowPopulation has no prioritized members: a PrioritizedRainbowReplay takes a "
-                                 "PrioritizedRainbowLearner of its own")
-            if not isinstance(r, RainbowReplay):
-                raise ValueError(f"expected RainbowReplays, got a {type(r).__name__}")
+        self._check_replays(replays)
         self.device = cuda_device(torch, device, replays[0].device)
         for r in replays:
             if r.device != self.device:
@@ -83,7 +89,7 @@ class RainbowPopulation:
         self.replays = replays
         lib = _native.lib
         self.batch_size = int(batch_size)
-        one = int(lib.mg_rainbow_learn_scratch_bytes(self.batch_size))
+        one = int(getattr(lib, self._scratch_entry)(self.batch_size))
         if one == 0:
             raise ValueError("batch_size must be in 1..1024")
         lrs, gammas, epss = (per_member(v, M, n) for v, n in ((lr, "lr"), (gamma, "gamma"), (eps, "eps")))
@@ -115,6 +121,18 @@ class RainbowPopulation:
         self._call(0)
 
     # ------------------------------------------------------------------ helpers
+    _scratch_entry = "mg_rainbow_learn_scratch_bytes"  # the library's size of one member's scratch
+    _store_many = staticmethod(store_rainbow_rollout_many)  # collect()'s store
+
+    @staticmethod
+    def _check_replays(replays):
+        for r in replays:
+            if isinstance(r, PrioritizedRainbowReplay):
+                raise ValueError("a RainbowPopulation has no prioritized members: a PrioritizedRainbowReplay takes a "
+                                 "PrioritizedRainbowPopulation, or a PrioritizedRainbowLearner of its own")
+            if not isinstance(r, RainbowReplay):
+                raise ValueError(f"expected RainbowReplays, got a {type(r).__name__}")
+
     def __len__(self):
         return len(self._members)
 
@@ -170,14 +188,12 @@ class RainbowPopulation:
         store_rainbow_rollout_many into self.replays: four launches beside the 4 M of the members in turn, each
         member's slice, replay and counter bit for bit the lone loop's. Returns the trajectory. Refuses a
         population whose replays are shared."""
-        from .rainbow_learn import store_rainbow_rollout_many
-
         if len({id(r) for r in self.replays}) != len(self.replays):
             raise ValueError("collect() appends each member's transitions to its own ring: this population's "
                              "rings are shared")
         obs0 = env.observe()
         traj = env.rollout_rainbow_many(num_steps, self.nets, opponent)
-        store_rainbow_rollout_many(self.replays, obs0, traj)
+        self._store_many(self.replays, obs0, traj)
         return traj
 
     # ------------------------------------------------------------------ learn
@@ -188,6 +204,10 @@ class RainbowPopulation:
         nothing is synchronised and nothing is drawn or uploaded by the host. Returns None, the one requested
         device tensor, or a tuple of the requested ones in the order loss [U, M], rows [U, M, B, 24], proj
         [U, M, B, 51], grads [U, M, P]."""
+        return self._learn(num_updates, return_loss, return_rows, return_proj, return_grads)
+
+    def _learn(self, num_updates, return_loss, return_rows, return_proj, return_grads, more=(), **extra):
+        """more: further optional output tensors, returned behind the four; extra: what _call takes besides."""
         torch = self._torch
         U, M, B = int(num_updates), len(self._members), self.batch_size
         if U < 0:
@@ -200,8 +220,8 @@ class RainbowPopulation:
             first = (ctypes.c_uint64 * M)(*(e.first_update for e in self._members))
             rc = _native.lib.mg_rainbow_noise_many(self._noise_seeds, first, M, U, noise.data_ptr(), self._stream())
             _native.check(rc, "mg_rainbow_noise_many")
-            self._call(U, noise, loss, rows, proj, grads)  # `noise` may go: the allocator is stream-ordered
-        out = tuple(t for t in (loss, rows, proj, grads) if t is not None)
+            self._call(U, noise, loss, rows, proj, grads, **extra)  # `noise` may go: the allocator is stream-ordered
+        out = tuple(t for t in (loss, rows, proj, grads, *more) if t is not None)
         return None if not out else out[0] if len(out) == 1 else out
 
     def sync_target(self, members=None):
@@ -283,3 +303,74 @@ class RainbowPopulation:
         self._members[dst].first_update = self._members[src].first_update
         self._members[dst].first_draw = self._members[src].first_draw
         self._call(0)
+
+
+class PrioritizedRainbowPopulation(RainbowPopulation):
+    """RainbowPopulation over M PrioritizedRainbowReplays (libmerging_hip.so's mg_rainbow_learn_prioritized_many):
+    every update draws each member's minibatch from its own tree, weights its rows' losses and writes loss_b +
+    prio_eps back as their priorities -- PrioritizedRainbowLearner's nine launches, for all members at once, nothing
+    synchronised. The trees belong to the replays, as in the lone class: copy_member copies no tree, and a
+    checkpoint of the population holds none (the replays' state_dict() does)."""
+
+    _scratch_entry = "mg_rainbow_learn_prioritized_scratch_bytes"
+    _store_many = staticmethod(store_prioritized_rollout_many)
+
+    def __init__(self, nets, replays, lr=0.001, gamma=0.99, batch_size: int = 32, seed=0, noise_seed=None,
+                 betas=(0.9, 0.999), eps=1e-8, device=None, beta=0.4, prio_eps=1e-5):
+        """RainbowPopulation's arguments, with replays M distinct PrioritizedRainbowReplays of one capacity on one
+        device, each with its own alpha (learning writes a member's tree, so a shared replay has no defined order);
+        then beta -- the importance weights' exponent, which learn() may override per call -- and prio_eps, each
+        one value or a sequence of M."""
+        replays = list(replays)
+        self.beta = self._betas(beta, len(replays))
+        self.prio_eps = [float(v) for v in per_member(prio_eps, len(replays), "prio_eps")]
+        if not all(v >= 0 for v in self.prio_eps):
+            raise ValueError("prio_eps must be >= 0")
+        super().__init__(nets, replays, lr, gamma, batch_size, seed, noise_seed, betas, eps, device)
+
+    @staticmethod
+    def _betas(beta, M):
+        out = [float(v) for v in per_member(beta, M, "beta")]
+        if not all(v > 0 for v in out):
+            raise ValueError("beta must be > 0")
+        return out
+
+    @staticmethod
+    def _check_replays(replays):
+        for r in replays:
+            if not isinstance(r, PrioritizedRainbowReplay):
+                raise ValueError(f"expected PrioritizedRainbowReplays, got a {type(r).__name__} (a RainbowReplay "
+                                 "takes a RainbowPopulation)")
+        if len({id(r) for r in replays}) != len(replays):
+            raise ValueError("a replay is listed twice: learning writes a member's tree, so two members on one "
+                             "replay have no defined order")
+
+    def _call(self, U, noise=None, loss=None, rows=None, proj=None, grads=None, beta=None, idx=None, weights=None):
+        """One call of mg_rainbow_learn_prioritized_many (see RainbowPopulation._call)."""
+        M = len(self._members)
+        per = (_native.PerMember * M)(*(
+            _native.PerMember(r._tree.data_ptr(), r.alpha, b, e)
+            for r, b, e in zip(self.replays, self.beta if beta is None else beta, self.prio_eps)))
+        rc = _native.lib.mg_rainbow_learn_prioritized_many(
+            self._buf.data_ptr(), self._table.data_ptr(), self._table_bytes, self._members, M,
+            self.replays[0].capacity, self.batch_size, U, ptr(noise), ptr(loss), ptr(rows), ptr(proj), ptr(grads),
+            self._packed.data_ptr(), self._stride, self._scratch.data_ptr(), self._scratch_bytes, per,
+            self.replays[0]._tree_bytes, ptr(idx), ptr(weights), self._stream())
+        _native.check(rc, "mg_rainbow_learn_prioritized_many")
+        for net in self.nets:
+            net._stale = True
+
+    def learn(self, num_updates: int = 1, return_loss: bool = False, return_rows: bool = False,
+              return_proj: bool = False, return_grads: bool = False, return_idx: bool = False,
+              return_weights: bool = False, beta=None):
+        """RainbowPopulation.learn with, behind its four outputs, idx [U, M, B] int64 (the sampled slots) and
+        weights [U, M, B] fp32. beta: this call's importance exponents, one value or a sequence of M (default:
+        the constructor's). loss [U, M] is each member's weighted mean; the priorities are updated from the
+        unweighted row losses."""
+        torch, M, B = self._torch, len(self._members), self.batch_size
+        beta = None if beta is None else self._betas(beta, M)
+        U = max(int(num_updates), 0)
+        idx = torch.empty((U, M, B), dtype=torch.int64, device=self.device) if return_idx else None
+        weights = torch.empty((U, M, B), dtype=torch.float32, device=self.device) if return_weights else None
+        return self._learn(num_updates, return_loss, return_rows, return_proj, return_grads, (idx, weights),
+                           beta=beta, idx=idx, weights=weights)
