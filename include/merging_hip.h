@@ -47,6 +47,12 @@
  *                     population -- up to 64 members' epsilon-greedy rollouts on slices of one env batch in
  *                     one launch, and their transitions into 64 rings in three; every member bit for bit a
  *                     lone mg_rollout_qnet / mg_replay_store
+ *   mg_rollout_qnet_league / mg_stats_reduce_many / mg_stats_reduce_many_scratch_bytes: league evaluation of
+ *                     such a population -- every ordered pair (ego i, opponent j) of up to 64 nets plays on its
+ *                     own slice of one env batch in one launch, and the batch's episode records become one
+ *                     total per pairing in two; every pairing bit for bit a lone mode-3 mg_rollout_qnet, every
+ *                     total a lone mg_stats_reduce (the reference's question, main.py:161-168: a net trained
+ *                     against L1, or in self-play, compared with the others as ego and as opponent)
  *   mg_rainbow_pack / mg_rainbow_packed_bytes / mg_rainbow_forward / mg_host_rainbow_head: RainbowDQN's
  *                     acting forward (scripts/ranbowdqn.py:517-548: noisy dueling C51 net, act()) -- bf16
  *                     MFMA layers, the distributional head in fp32 in a documented order
@@ -437,6 +443,30 @@ int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const m
                          uint64_t first_step, int32_t num_steps, const mg_qnet_actor* actors, int32_t out_dim,
                          int32_t opponent_mode, uint32_t flags, void* stream);
 
+/* ---- a league: every ordered pair of `nets` nets in one launch (additive to ABI 21) ----------------
+ * Cross-play of nets (1 .. 64) packed Q-nets of one out_dim on ONE env batch of n = nets * nets * n_pair envs:
+ * pairing p = i nets + j owns envs [p n_pair, (p + 1) n_pair), where net i is the ego and net j its opponent
+ * through opponent mode 3 (the diagonal i == j too: the net against a copy of itself on the mode-3 path, not
+ * mode 2). The draws are keyed by the ego's seed; each side explores by its own net's threshold. Pairing p is
+ * bit for bit mg_rollout_qnet on its slice alone: n = n_pair, env_offset + p n_pair, seed = league[i].seed, net =
+ * league[i].net, greedy_threshold = league[i]'s, opponent_mode 3, opp_net = league[j].net, opp_greedy_threshold =
+ * league[j]'s. The pairing is a grid dimension: nets^2 * ceil(n_pair / 1024) blocks, each reading its two nets'
+ * entries from the kernel argument (nets entries name nets^2 pairings), so a call allocates and synchronises
+ * nothing. state, traj and stats are the whole batch's; every traj pointer is optional (an evaluation that reads
+ * only the statistics records passes a zeroed mg_traj). n_pair must be a multiple of 64. Refused before any
+ * launch: nets outside 1 .. 64, n_pair < 0 or no multiple of 64, a batch past the grid limit, a NULL league, a
+ * NULL or misaligned net; n_pair == 0 or num_steps == 0 returns 0 and launches nothing. */
+typedef struct mg_league_net {
+  const void* net;  /* packed Q-net (mg_qnet_pack), 16-byte aligned */
+  uint64_t seed;    /* of the pairings where this net is the ego */
+  uint64_t greedy_threshold;
+} mg_league_net;
+
+int mg_rollout_qnet_league(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                           const mg_stats* stats, int64_t n_pair, int32_t nets, int64_t env_offset,
+                           uint64_t first_step, int32_t num_steps, const mg_league_net* league, int32_t out_dim,
+                           uint32_t flags, void* stream);
+
 /* ---- h-DQN acting loop (scripts/hdqn.py:280-323) ----------------------------------------------
  * The per-step outputs of mg_rollout_hdqn besides mg_traj, [T, n] fp32 each (NULL skips one):
  * exactly the goal columns and intrinsic reward hdqn.py's lower-level store_transition takes
@@ -566,6 +596,17 @@ int mg_replay_sample(const float* rows, const uint64_t* counter, int64_t capacit
 size_t mg_stats_reduce_scratch_bytes(int64_t n);
 int mg_stats_reduce(const mg_episode_stats* rec, int64_t n, mg_stats_totals* totals, void* scratch,
                     size_t scratch_bytes, void* stream);
+
+/* (additive to ABI 21) mg_stats_reduce on `segments` (1 .. 4096) equal runs of the records at once:
+ * totals[s] = records [s n_segment, (s + 1) n_segment) summed in mg_stats_reduce's order, bit for bit what
+ * mg_stats_reduce(rec + s n_segment, n_segment, ...) gives -- the members of mg_rollout_qnet_many or the pairings
+ * of mg_rollout_qnet_league. The same two launches with the segment as a grid dimension. scratch: at least
+ * mg_stats_reduce_many_scratch_bytes(n_segment, segments) = segments * mg_stats_reduce_scratch_bytes(n_segment)
+ * bytes (0 for segments outside 1 .. 4096), 16-byte aligned; rec 16-byte, totals (segments device
+ * mg_stats_totals) 8-byte aligned. n_segment == 0 gives every segment zero counts and -0.0 sums. */
+size_t mg_stats_reduce_many_scratch_bytes(int64_t n_segment, int32_t segments);
+int mg_stats_reduce_many(const mg_episode_stats* rec, int64_t n_segment, int32_t segments, mg_stats_totals* totals,
+                         void* scratch, size_t scratch_bytes, void* stream);
 
 /* Resets the envs whose mask byte is non-zero (mask == NULL: all n) and writes their reset
  * observation to out->obs / out->rec64 when given. Replaces MergeEnv.reset (merging_env.py:208-230). */

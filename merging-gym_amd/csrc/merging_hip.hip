@@ -216,7 +216,7 @@ int mg_rollout_qnet(const mg_params* params, const mg_state* state, const mg_tra
   R.out_dim = out_dim, R.fin = finish_bound(*params);
   R.net = static_cast<const uint8_t*>(net), R.opp_net = static_cast<const uint8_t*>(opp_net);
   R.greedy_thr = greedy_threshold, R.opp_greedy_thr = opp_greedy_threshold;
-  launch(qnet_rollout_instance<false>(opponent_mode, out_dim > MG_NUM_ACTIONS), grid_blocks(n, kQWsEnvs), kQWsThreads,
+  launch(qnet_rollout_instance<QRollout>(opponent_mode, out_dim > MG_NUM_ACTIONS), grid_blocks(n, kQWsEnvs), kQWsThreads,
          static_cast<hipStream_t>(stream), R);
   return finish_launch("mg_rollout_qnet");
 }
@@ -244,10 +244,43 @@ int mg_rollout_qnet_many(const mg_params* params, const mg_state* state, const m
   QRollout R = make_rollout<QRollout>(params, state, traj, stats, 0, first_step, env_offset, n, num_steps, flags);
   R.out_dim = out_dim, R.fin = finish_bound(*params);
   const QRolloutMany A = make_qrollout_many(R, n_member, actors, members, opponent_mode);
-  launch(qnet_rollout_instance<true>(opponent_mode, out_dim > MG_NUM_ACTIONS),
+  launch(qnet_rollout_instance<QRolloutMany>(opponent_mode, out_dim > MG_NUM_ACTIONS),
          static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kQWsThreads,
          static_cast<hipStream_t>(stream), A);
   return finish_launch("mg_rollout_qnet_many");
+}
+
+int mg_rollout_qnet_league(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                           const mg_stats* stats, int64_t n_pair, int32_t nets, int64_t env_offset,
+                           uint64_t first_step, int32_t num_steps, const mg_league_net* league, int32_t out_dim,
+                           uint32_t flags, void* stream) {
+  const char* const who = "mg_rollout_qnet_league: %s";
+  if (!members_ok(nets)) return fail(hipErrorInvalidValue, who, "need 1 <= nets <= 64");
+  if (n_pair < 0) return fail(hipErrorInvalidValue, who, "n_pair < 0");
+  if (n_pair % 64 != 0)
+    return fail(hipErrorInvalidValue, who,
+                "n_pair must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole, so no "
+                "two pairings may share one)");
+  const int64_t pairs = static_cast<int64_t>(nets) * nets;
+  // the envs within what a grid of kBlock-env blocks covers (check_common's limit), and the kernel's own blocks
+  if (n_pair > (static_cast<int64_t>(0x7fffffff) * kBlock) / pairs ||
+      pairs * ((n_pair + kQWsEnvs - 1) / kQWsEnvs) > 0x7fffffff)
+    return fail(hipErrorInvalidValue, who, "nets * nets * n_pair exceeds the grid limit");
+  const int64_t n = n_pair * pairs;
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (!league) return fail(hipErrorInvalidValue, who, "league is NULL (nets mg_league_net entries)");
+  if (int e = check_qrollout_dims(who, num_steps, out_dim)) return e;
+  if (int e = check_league_nets(league, nets)) return e;
+  if (int e = check_traj(traj)) return e;
+  if (n_pair == 0 || num_steps == 0) return 0;
+  QRollout R = make_rollout<QRollout>(params, state, traj, stats, 0, first_step, env_offset, n, num_steps, flags);
+  R.out_dim = out_dim, R.fin = finish_bound(*params);
+  const QRolloutLeague A = make_qrollout_league(R, n_pair, league, nets);
+  // mode 3's instance is the checked one whatever out_dim is (qnet_rollout_instance)
+  launch(qnet_rollout_ws_kernel<3, true, QRolloutLeague>,
+         static_cast<unsigned>(pairs) * static_cast<unsigned>(A.blocks_per_pair), kQWsThreads,
+         static_cast<hipStream_t>(stream), A);
+  return finish_launch("mg_rollout_qnet_league");
 }
 
 int mg_rollout_hdqn(const mg_params* params, const mg_state* state, const mg_traj* traj,
@@ -393,6 +426,37 @@ int mg_stats_reduce(const mg_episode_stats* rec, int64_t n, mg_stats_totals* tot
     hipLaunchKernelGGL(stats_reduce_kernel, dim3(static_cast<unsigned>(nb)), dim3(kRedThreads), 0, st, rec, n, part);
   hipLaunchKernelGGL(stats_reduce_final_kernel, dim3(1), dim3(kRedThreads), 0, st, part, nb, totals);
   return finish_launch("mg_stats_reduce");
+}
+
+constexpr int32_t kRedMaxSegments = 4096;  // the league's 64 x 64 pairings; the grid's second dimension holds 65,535
+
+size_t mg_stats_reduce_many_scratch_bytes(int64_t n_segment, int32_t segments) {
+  if (segments < 1 || segments > kRedMaxSegments) return 0;
+  return static_cast<size_t>(segments) * mg_stats_reduce_scratch_bytes(n_segment);
+}
+
+int mg_stats_reduce_many(const mg_episode_stats* rec, int64_t n_segment, int32_t segments, mg_stats_totals* totals,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+  const char* const who = "mg_stats_reduce_many: %s";
+  if (segments < 1 || segments > kRedMaxSegments) return fail(hipErrorInvalidValue, who, "need 1 <= segments <= 4096");
+  if (n_segment < 0) return fail(hipErrorInvalidValue, who, "n_segment < 0");
+  if (!totals || (n_segment > 0 && !rec)) return fail(hipErrorInvalidValue, who, "NULL pointer");
+  if (misaligned(rec, 15) || misaligned(scratch, 15) || misaligned(totals, 7))
+    return fail(hipErrorInvalidValue, who, "rec and scratch must be 16-byte, totals 8-byte aligned");
+  // before the scratch size, which is only then a product that fits
+  const int64_t nb = n_segment / kRedEnvs + (n_segment % kRedEnvs != 0);
+  if (nb > 0x7fffffff) return fail(hipErrorInvalidValue, who, "n_segment exceeds the grid limit");
+  if (n_segment > 0 && (!scratch || scratch_bytes < mg_stats_reduce_many_scratch_bytes(n_segment, segments)))
+    return fail(hipErrorInvalidValue, who,
+                "scratch smaller than mg_stats_reduce_many_scratch_bytes(n_segment, segments)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  mg_stats_totals* part = static_cast<mg_stats_totals*>(scratch);
+  const unsigned S = static_cast<unsigned>(segments);
+  if (nb > 0)
+    hipLaunchKernelGGL(stats_reduce_many_kernel, dim3(static_cast<unsigned>(nb), S), dim3(kRedThreads), 0, st, rec,
+                       n_segment, nb, part);
+  hipLaunchKernelGGL(stats_reduce_final_many_kernel, dim3(S), dim3(kRedThreads), 0, st, part, nb, totals);
+  return finish_launch("mg_stats_reduce_many");
 }
 
 int mg_host_step(const mg_params* params, const mg_state* state, const int8_t* a1, const int8_t* a2,

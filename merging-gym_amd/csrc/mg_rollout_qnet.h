@@ -1,6 +1,7 @@
 // mg_rollout_qnet.h -- config 5, the Q-net policy rollout: FinishBound, QRollout, qnet_rollout_ws_kernel, and
-// the same kernel with the member in the grid (QRolloutMany, QMemberRollout, the MANY instances), and the host
-// side of mg_rollout_qnet and mg_rollout_qnet_many: their shared checks, the launch's fill, the choice of instance.
+// the same kernel with the member in the grid (QRolloutMany, QMemberRollout, the member instances) or every
+// ordered pair of K nets in the grid (QRolloutLeague, the league instance), and the host side of mg_rollout_qnet,
+// mg_rollout_qnet_many and mg_rollout_qnet_league: their shared checks, the launch's fill, the choice of instance.
 // A part of the one translation unit merging_hip.hip (see its head comment).
 #pragma once
 
@@ -131,6 +132,25 @@ struct QRolloutMany {
   QMember mem[kMaxMembers];
 };
 static_assert(sizeof(QRolloutMany) <= 4096, "HIP's kernel argument limit");
+
+// ---- every ordered pair in the grid (mg_rollout_qnet_league; the kernel's league instance): one batch of
+// nets * nets * n_pair envs, pairing p = i nets + j owning envs [p n_pair, (p + 1) n_pair), where net i is the ego
+// and net j the opponent (OPP 3), each with its own threshold, the draws keyed by the ego's seed. K entries name
+// K * K pairings, so 4,096 of them fit the argument that holds 64 members.
+struct QLeagueNet {
+  const uint8_t* net;
+  uint64_t seed;
+  uint64_t greedy_thr;
+};
+struct QRolloutLeague {
+  QRollout R;               // shared: n = nets * nets * n_pair (the row stride); net, seed, thresholds unused
+  int64_t n_pair;           // a multiple of 64: no won-mask word spans two pairings
+  int32_t blocks_per_pair;  // ceil(n_pair / kQWsEnvs)
+  int32_t nets;             // K
+  QLeagueNet net[kMaxMembers];
+};
+static_assert(sizeof(QLeagueNet) == 24, "three words per net");
+static_assert(sizeof(QRolloutLeague) <= 4096, "HIP's kernel argument limit");
 
 // What the role functions see of a member's block: the shared launch by reference (the kernel
 // argument, never copied) and the member's own scalars, block-uniform. Field for field QRollout's names.
@@ -588,6 +608,31 @@ __device__ __forceinline__ int64_t qws_block_base(const QRolloutMany& A) {
   const int local = static_cast<int>(blockIdx.x) - m * A.blocks_per_member;
   return m * A.n_member + static_cast<int64_t>(local) * kQWsEnvs;
 }
+// The league: block b serves pairing p = b div blocks_per_pair, ego p div K against opponent p mod K; the view is a
+// member's, its two nets and thresholds picked from two entries of the list. It is a QMemberRollout under a name
+// of its own: with the plain type the league instance shared the member instances' role-function instantiations
+// (two callers of each where there was one), and qnet_rollout_ws_kernel<3, true, QRolloutMany> came out with 232
+// VGPRs instead of its 234. Instantiated apart, every earlier instance compiles as before, the league one as its twin.
+struct QPairRollout : QMemberRollout {};
+__device__ __forceinline__ int qws_pairing(const QRolloutLeague& A) {
+  return static_cast<int>(blockIdx.x) / A.blocks_per_pair;
+}
+__device__ __forceinline__ QPairRollout qws_block_view(const QRolloutLeague& A) {
+  const int p = qws_pairing(A);
+  const int i = p / A.nets, j = p - i * A.nets;
+  const QLeagueNet& ego = A.net[i];
+  const QLeagueNet& opp = A.net[j];
+  return QPairRollout{{A.R.P,          A.R.R0,         A.R.S,          A.R.T,
+                       A.R.St,         ego.net,        opp.net,        ego.seed,
+                       A.R.first_step, ego.greedy_thr, opp.greedy_thr, A.R.env_offset,
+                       A.R.n,          (p + 1) * A.n_pair, A.R.num_steps, A.R.out_dim,
+                       A.R.flags,      A.R.fin}};
+}
+__device__ __forceinline__ int64_t qws_block_base(const QRolloutLeague& A) {
+  const int p = qws_pairing(A);
+  const int local = static_cast<int>(blockIdx.x) - p * A.blocks_per_pair;
+  return p * A.n_pair + static_cast<int64_t>(local) * kQWsEnvs;
+}
 
 // CHECKED: a greedy action may fall outside action_dict (a net with out_dim > 5): the lockstep step
 // carries the KeyError selects. Every other launch takes CHECKED = false (-2 % on the ego-only
@@ -599,10 +644,12 @@ __device__ __forceinline__ int64_t qws_block_base(const QRolloutMany& A) {
 // batch (R.n); the Philox env index stays env_offset + i, i within the batch, so member m is a lone launch
 // on n_member envs at env_offset + m n_member. The member's scalars are block-uniform: read once from the
 // kernel argument by a uniform index (scalar loads).
-template <int OPP, bool CHECKED, bool MANY = false>
-__global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws_kernel(
-    const std::conditional_t<MANY, QRolloutMany, QRollout> A) {
-  decltype(auto) R = qws_block_view(A);  // QRollout itself, or the member's QMemberRollout
+// ARG: the form of the argument, which is all that tells the three apart -- QRollout (lone), QRolloutMany (the member
+// in the grid) or QRolloutLeague (every ordered pair of K nets in the grid, mg_rollout_qnet_league: a member's block
+// whose two nets are entries i and j of one list; only the OPP 3, checked instance exists).
+template <int OPP, bool CHECKED, class ARG = QRollout>
+__global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws_kernel(const ARG A) {
+  decltype(auto) R = qws_block_view(A);  // QRollout itself, or the member's / the pairing's QMemberRollout
   constexpr int kIlp = kQWsIlp;
   constexpr int kEnvs = kQWsEnvs;  // envs per block
   constexpr int kHalf = kQWsHalf;  // envs per group
@@ -755,15 +802,22 @@ __global__ __launch_bounds__(kQWsThreads, kQWsWavesPerSimd) void qnet_rollout_ws
 }
 
 // ============================================================================ the host side of a call
-// What mg_rollout_qnet and mg_rollout_qnet_many share. Each keeps its own order of checks (the lone call looks at
-// its net before out_dim, the member call at every member's nets after the mode): the pieces are shared, not the walk.
+// What mg_rollout_qnet, mg_rollout_qnet_many and mg_rollout_qnet_league share. Each keeps its own order of checks
+// (the lone call looks at its net before out_dim, the member call at every member's nets after the mode, the league
+// call has no mode): the pieces are shared, not the walk.
 // The launch's fill is make_rollout (mg_launch.h) and two more fields, out_dim and fin, set where it is made.
+
+// num_steps and out_dim; who: the text's frame, "%s" or "<entry point>: %s"
+int check_qrollout_dims(const char* who, int32_t num_steps, int32_t out_dim) {
+  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
+    return fail(hipErrorInvalidValue, who, "need num_steps >= 0 and 1 <= out_dim <= 8");
+  return 0;
+}
 
 // num_steps and out_dim, then the mode: neighbours in both orders. The member call's texts carry its name.
 int check_qrollout_dims_mode(bool many, int32_t num_steps, int32_t out_dim, int32_t opponent_mode) {
   const char* const who = many ? "mg_rollout_qnet_many: %s" : "%s";
-  if (num_steps < 0 || out_dim < 1 || out_dim > kLMaxOut)
-    return fail(hipErrorInvalidValue, who, "need num_steps >= 0 and 1 <= out_dim <= 8");
+  if (int e = check_qrollout_dims(who, num_steps, out_dim)) return e;
   if (opponent_mode < 0 || opponent_mode > 3)
     return fail(hipErrorInvalidValue, who,
                 many ? "opponent_mode must be 0 (None), 1 (uniform), 2 (same net) or 3 (each member's opp_net)"
@@ -795,13 +849,31 @@ QRolloutMany make_qrollout_many(const QRollout& R, int64_t n_member, const mg_qn
 
 // The instance for a launch. checked: an argmax may name an action past action_dict (out_dim > 5); a net opponent's
 // instances are always checked. They come out in the code object in the order of first naming: the lone call's.
-template <bool MANY>
-auto qnet_rollout_instance(int32_t opponent_mode, bool checked)
-    -> void (*)(std::conditional_t<MANY, QRolloutMany, QRollout>) {
-  return opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true, MANY> : qnet_rollout_ws_kernel<0, false, MANY>)
-         : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true, MANY> : qnet_rollout_ws_kernel<1, false, MANY>)
-         : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true, MANY>
-                              : qnet_rollout_ws_kernel<3, true, MANY>;
+template <class ARG>
+auto qnet_rollout_instance(int32_t opponent_mode, bool checked) -> void (*)(ARG) {
+  return opponent_mode == 0   ? (checked ? qnet_rollout_ws_kernel<0, true, ARG> : qnet_rollout_ws_kernel<0, false, ARG>)
+         : opponent_mode == 1 ? (checked ? qnet_rollout_ws_kernel<1, true, ARG> : qnet_rollout_ws_kernel<1, false, ARG>)
+         : opponent_mode == 2 ? qnet_rollout_ws_kernel<2, true, ARG>
+                              : qnet_rollout_ws_kernel<3, true, ARG>;
+}
+
+// ---- mg_rollout_qnet_league
+// Every net of the list: each is some pairing's ego and some pairing's opponent.
+int check_league_nets(const mg_league_net* league, int32_t nets) {
+  for (int k = 0; k < nets; ++k)
+    if (!league[k].net || misaligned(league[k].net, 15)) {
+      std::snprintf(g_err, sizeof(g_err), "mg_rollout_qnet_league: net %d: net must be a 16-byte aligned packed Q-net", k);
+      return static_cast<int>(hipErrorInvalidValue);
+    }
+  return 0;
+}
+
+// The league call's argument: the launch (n = nets * nets * n_pair; seed, nets, thresholds unused), the entries.
+QRolloutLeague make_qrollout_league(const QRollout& R, int64_t n_pair, const mg_league_net* league, int32_t nets) {
+  QRolloutLeague A{R, n_pair, static_cast<int32_t>(grid_blocks(n_pair, kQWsEnvs)), nets};
+  for (int k = 0; k < nets; ++k)
+    A.net[k] = QLeagueNet{static_cast<const uint8_t*>(league[k].net), league[k].seed, league[k].greedy_threshold};
+  return A;
 }
 
 }  // namespace

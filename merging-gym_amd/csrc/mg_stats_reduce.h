@@ -15,6 +15,7 @@ namespace {
 //          identity), then the block folds its kRedThreads values in halves (v[t] += v[t + o],
 //          o = 128, 64, ..., 1) -> partial b;
 //   pass 2 (one block): thread t adds partials t, t + 256, ... in order onto -0.0, then the same fold.
+// mg_stats_reduce_many runs both passes on many equal runs of the records at once (stats_reduce_many_kernel below).
 // The counts are exact int64 sums; the fp64 ones are ret[0], ret[1], ret_main and q_eval. Replaces the logging loops' running totals (hdqn.py:330-346,
 // main.py:221-228) for a whole batch; a torch sum over strided record columns took 7.6 ms at 2^20
 // envs (BENCH_r03 episodes.reduce_ms) for 64 MB of records.
@@ -49,14 +50,15 @@ __device__ __forceinline__ void red_store(mg_stats_totals* out, double (*sd)[kRe
   *out = o;
 }
 
-__global__ __launch_bounds__(kRedThreads) void stats_reduce_kernel(const mg_episode_stats* rec, int64_t n,
-                                                                   mg_stats_totals* part) {
+// Pass 1 of one run of n records: block `block` (of this run's own blocks) -> part[block].
+__device__ __forceinline__ void red_pass1(const mg_episode_stats* rec, int64_t n, unsigned block,
+                                          mg_stats_totals* part) {
   __shared__ double sd[kRedSums][kRedThreads];
   __shared__ int64_t si[6][kRedThreads];
   const int t = threadIdx.x;
   double a0 = -0.0, a1 = -0.0, a2 = -0.0, a3 = -0.0;
   int64_t c[6] = {0, 0, 0, 0, 0, 0};
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kRedEnvs + t;
+  const int64_t base = static_cast<int64_t>(block) * kRedEnvs + t;
 #pragma unroll
   for (int j = 0; j < kRedPer; ++j) {
     const int64_t i = base + j * kRedThreads;
@@ -85,11 +87,11 @@ __global__ __launch_bounds__(kRedThreads) void stats_reduce_kernel(const mg_epis
 #pragma unroll
   for (int k = 0; k < 6; ++k) si[k][t] = c[k];
   red_fold(sd, si, t);
-  if (t == 0) red_store(part + blockIdx.x, sd, si);
+  if (t == 0) red_store(part + block, sd, si);
 }
 
-__global__ __launch_bounds__(kRedThreads) void stats_reduce_final_kernel(const mg_stats_totals* part, int64_t nb,
-                                                                         mg_stats_totals* out) {
+// Pass 2 of one run: its nb partials -> *out.
+__device__ __forceinline__ void red_pass2(const mg_stats_totals* part, int64_t nb, mg_stats_totals* out) {
   __shared__ double sd[kRedSums][kRedThreads];
   __shared__ int64_t si[6][kRedThreads];
   const int t = threadIdx.x;
@@ -109,6 +111,31 @@ __global__ __launch_bounds__(kRedThreads) void stats_reduce_final_kernel(const m
   for (int q = 0; q < 6; ++q) si[q][t] = c[q];
   red_fold(sd, si, t);
   if (t == 0) red_store(out, sd, si);
+}
+
+__global__ __launch_bounds__(kRedThreads) void stats_reduce_kernel(const mg_episode_stats* rec, int64_t n,
+                                                                   mg_stats_totals* part) {
+  red_pass1(rec, n, blockIdx.x, part);
+}
+
+__global__ __launch_bounds__(kRedThreads) void stats_reduce_final_kernel(const mg_stats_totals* part, int64_t nb,
+                                                                         mg_stats_totals* out) {
+  red_pass2(part, nb, out);
+}
+
+// The same two passes over `segments` runs of n_segment records each, the segment in the grid (mg_stats_reduce_many):
+// segment s reads records [s n_segment, (s + 1) n_segment), keeps its nb = ceil(n_segment / kRedEnvs) partials at
+// part[s nb ..] and writes out[s] -- each bit for bit the lone pair on that run, whose order never looks past it.
+__global__ __launch_bounds__(kRedThreads) void stats_reduce_many_kernel(const mg_episode_stats* rec, int64_t n_segment,
+                                                                        int64_t nb, mg_stats_totals* part) {
+  const int64_t s = blockIdx.y;
+  red_pass1(rec + s * n_segment, n_segment, blockIdx.x, part + s * nb);
+}
+
+__global__ __launch_bounds__(kRedThreads) void stats_reduce_final_many_kernel(const mg_stats_totals* part, int64_t nb,
+                                                                              mg_stats_totals* out) {
+  const int64_t s = blockIdx.x;
+  red_pass2(part + s * nb, nb, out + s);
 }
 
 // goal_status of n (dx1, v2) pairs, the function the h-DQN kernel evaluates (tests, evaluation)

@@ -37,6 +37,10 @@ def __getattr__(name):  # ReplayRing and DQNLearner load the native library on f
         from . import rainbow_learn
 
         return getattr(rainbow_learn, name)
+    if name in ("device_totals_many", "summarize_segments"):  # league evaluation: K x K totals and their summaries
+        from . import distributed
+
+        return getattr(distributed, name)
     raise AttributeError(name)
 
 ENV_IDS = {

@@ -93,6 +93,12 @@ class QnetActor(_c.Structure):
                 ("opp_greedy_threshold", _c.c_uint64)]
 
 
+class LeagueNet(_c.Structure):
+    """struct mg_league_net: one net of mg_rollout_qnet_league -- its packed net, the seed of the pairings where
+    it is the ego, and its greedy threshold on either side."""
+    _fields_ = [("net", _P), ("seed", _c.c_uint64), ("greedy_threshold", _c.c_uint64)]
+
+
 class Stats(_c.Structure):
     _fields_ = [("rec", _P)]  # mg_episode_stats [n] (64 bytes each, see EPISODE_STATS_DTYPE)
 
@@ -213,6 +219,15 @@ def _load(path=LIB_PATH):
                                          _c.POINTER(Transitions), _c.c_int64, _c.c_int32, _c.c_int32, _P,
                                          _c.c_size_t, _P]
     for f in (lib.mg_rollout_qnet_many, lib.mg_replay_store_many):
+        f.restype = _c.c_int
+    # league evaluation (additive to ABI 21): every ordered pair of nets in one launch, one total per segment in two
+    lib.mg_rollout_qnet_league.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _c.c_int64,
+                                           _c.c_uint64, _c.c_int32, _c.POINTER(LeagueNet), _c.c_int32, _c.c_uint32,
+                                           _P]
+    lib.mg_stats_reduce_many_scratch_bytes.argtypes = [_c.c_int64, _c.c_int32]
+    lib.mg_stats_reduce_many_scratch_bytes.restype = _c.c_size_t
+    lib.mg_stats_reduce_many.argtypes = [_P, _c.c_int64, _c.c_int32, _P, _P, _c.c_size_t, _P]
+    for f in (lib.mg_rollout_qnet_league, lib.mg_stats_reduce_many):
         f.restype = _c.c_int
     # Rainbow acting (additive to ABI 21): the packed net, its forward, the fused rollout, the host head
     lib.mg_rainbow_packed_bytes.restype = _c.c_size_t

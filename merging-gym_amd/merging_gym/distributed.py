@@ -125,6 +125,53 @@ def device_totals(records, events=None):
     return out
 
 
+MAX_SEGMENTS = 4096  # mg_stats_reduce_many's limit: the 64 x 64 pairings of a league
+
+
+def device_totals_many(records, segments):
+    """device_totals for `segments` (1..4096) equal runs of the [n, 8] f64 device records at once: a
+    [segments, 10] int64 device tensor whose row s is device_totals(records[s n / segments : (s + 1) n / segments])
+    to the bit, by ONE mg_stats_reduce_many (the same two launches with the segment in the grid) on the current
+    stream, no synchronisation. The scratch is allocated on that stream, as device_totals allocates its own."""
+    import ctypes
+
+    import torch
+
+    from . import _native
+
+    n, S = records.shape[0], int(segments)
+    if not 1 <= S <= MAX_SEGMENTS or n % S:
+        raise ValueError(f"{n} records are not {S} equal runs (1..{MAX_SEGMENTS} of them)")
+    dev = records.device
+    out = torch.empty((S, NUM_SUMS + NUM_COUNTS), dtype=torch.int64, device=dev)
+    words = max(1, (_native.lib.mg_stats_reduce_many_scratch_bytes(n // S, S) + 7) // 8)
+    stream = torch.cuda.current_stream(dev)
+    with torch.cuda.stream(stream):
+        scratch = torch.empty(words, dtype=torch.int64, device=dev)
+    rc = _native.lib.mg_stats_reduce_many(ctypes.c_void_p(records.data_ptr()), n // S, S,
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+                                          scratch.numel() * 8, ctypes.c_void_p(stream.cuda_stream))
+    _native.check(rc, "mg_stats_reduce_many")
+    return out
+
+
+def summarize_segments(totals):
+    """[S, 10] totals (device_totals_many's rows) -> summarize_partials' dict with one [S] CPU tensor per key
+    (float64; `completed` int64): entry s is summarize_partials(totals[s])'s number exactly -- the same
+    arithmetic, each sum added onto 0.0 and divided by max(completed, 1). One host copy."""
+    import torch
+
+    t = totals.reshape(-1, NUM_SUMS + NUM_COUNTS).cpu()
+    sums = t[:, :NUM_SUMS].contiguous().view(torch.float64) + 0.0  # summarize_partials starts each sum at 0.0
+    c = t[:, NUM_SUMS:]
+    ep = c[:, 0].clamp(min=1).to(torch.float64)
+    cf = c.to(torch.float64)  # exact: the counts are far below 2^53
+    return {"completed": c[:, 0].clone(), "mean_return_ego": sums[:, 0] / ep, "mean_return_opp": sums[:, 1] / ep,
+            "mean_ep_reward_main": sums[:, 2] / ep, "collision_rate": cf[:, 1] / ep, "ego_first_rate": cf[:, 2] / ep,
+            "win_rate_main": cf[:, 4] / ep, "win_rate_hdqn": cf[:, 5] / ep, "mean_length": cf[:, 3] / ep,
+            "mean_q_eval": sums[:, 3] / ep}
+
+
 def partial_stats(returns, counts, q_eval=None, events=None):
     """This shard's totals as one [10] int64 tensor on the stats' device: the three return sums
     (r1_accumulate, r2_accumulate, main.py's filtered ep_reward; f64, bit-preserved), the q_eval sum

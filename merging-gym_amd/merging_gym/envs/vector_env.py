@@ -421,6 +421,80 @@ class MergeVecEnv:
                                       self._p_ref, self._s_ref, traj, self._st_ref, self.num_envs // M, M,
                                       self.env_offset, k0, T, actors, out_dim, mode, self._flags, self._stream()))
 
+    def rollout_qnet_league(self, num_steps: int, qnets, seed, episilo=0.7, first_step=None,
+                            final_observation: bool = True, won_mask: bool = True, trajectory: bool = True):
+        """Cross-play of K nets in ONE launch: qnets is a list of K QNets (in_dim 10, one out_dim), and every
+        ordered pair (ego i, opponent j) plays on its own slice of the batch -- pairing p = i K + j owns envs
+        [p n, (p + 1) n), n = num_envs / K^2 (a multiple of 64), where qnets[i] acts as the ego and qnets[j] as
+        its opponent on the swapped observation (rollout_qnet's net opponent, main.py's Strategy_OP "L1").
+        seed and episilo are each one value or a sequence of K: the draws of pairing (i, j) are keyed by seed[i],
+        the ego explores with episilo[i] and the opponent with episilo[j]. Pairing p is bit for bit what a lone
+        MergeVecEnv(n, env_offset=self.env_offset + p n) holding the slice's state gives for
+        rollout_qnet(num_steps, qnets[i], seed[i], opponent=qnets[j], episilo=episilo[i],
+        opp_episilo=episilo[j]). The diagonal (i, i) is the net against a copy of itself through that same
+        other-net path (opponent mode 3 with opp_net = net); it is NOT opponent="self", mode 2's kernel.
+        Frozen checkpoints are evaluated by putting their QNets in the list and reading the sub-block.
+        Returns the same [T, N, ...] dict as rollout_qnet, or, with trajectory=False, None: the kernel then
+        gets no trajectory pointer and writes only the state and the episode records (an evaluation reads
+        league_summary and needs no [T, N, 10] observations). The K entries travel in the kernel argument: a
+        call allocates and synchronises nothing."""
+        from ..policy import greedy_threshold
+
+        nat = self._nat
+        qnets = list(qnets)
+        K = len(qnets)
+        if not 1 <= K <= MAX_MEMBERS:
+            raise ValueError(f"rollout_qnet_league takes 1..{MAX_MEMBERS} nets, got {K}")
+        if self.num_envs % (K * K) or (self.num_envs // (K * K)) % 64:
+            raise ValueError(f"num_envs = {self.num_envs} must be {K}^2 = {K * K} slices of a multiple of 64 envs "
+                             "(a won-mask word covers 64 envs, so two pairings must not share one)")
+        out_dim = qnets[0].out_dim
+        if any(q.out_dim != out_dim for q in qnets):
+            raise ValueError("the nets of one launch share one out_dim")
+        if any(q.in_dim != _OBS_DIM for q in qnets):
+            raise ValueError("the fused rollout feeds the 10-value observation: the nets need in_dim 10")
+        seeds, eps = per_member(seed, K, "seed"), per_member(episilo, K, "episilo")
+        league = (nat.LeagueNet * K)()
+        for k in range(K):
+            league[k] = nat.LeagueNet(qnets[k].packed.data_ptr(), int(seeds[k]) & U64, greedy_threshold(eps[k]))
+        call = lambda traj, k0, T: nat.lib.mg_rollout_qnet_league(  # noqa: E731
+            self._p_ref, self._s_ref, traj, self._st_ref, self.num_envs // (K * K), K, self.env_offset, k0, T,
+            league, out_dim, self._flags, self._stream())
+        if trajectory:
+            return self._qnet_rollout("mg_rollout_qnet_league", int(num_steps), first_step, final_observation,
+                                      won_mask, call)
+        k0 = self._step_idx if first_step is None else int(first_step)
+        nat.check(call(ctypes.byref(nat.Traj()), k0 & U64, int(num_steps)), "mg_rollout_qnet_league")
+        self._step_idx = k0 + int(num_steps)
+        return None
+
+    def member_totals(self, members: int):
+        """The episode statistics of each of `members` (1..4096) equal slices of the batch -- rollout_qnet_many's
+        members, rollout_qnet_league's K^2 pairings -- as one [members, 10] int64 device tensor, row m what
+        distributed.partial_stats gives for slice m's records to the bit. One mg_stats_reduce_many (two launches)
+        on the current stream, whatever `members` is; no synchronisation."""
+        from ..distributed import MAX_SEGMENTS, device_totals_many
+
+        if self._ep_stats is None:
+            raise ValueError("built with episode_stats=False")
+        M = int(members)
+        if not 1 <= M <= MAX_SEGMENTS or self.num_envs % M:
+            raise ValueError(f"num_envs = {self.num_envs} is not {M} equal slices (1..{MAX_SEGMENTS} of them)")
+        return device_totals_many(self._ep_stats, M)
+
+    def league_summary(self, nets: int):
+        """The payoff matrices of a league of K = `nets` nets (rollout_qnet_league's K^2 slices): a dict with
+        episode_summary()'s keys, each value a [K, K] float64 CPU tensor (`completed`: int64) whose entry [i, j]
+        is that quantity for ego i against opponent j -- exactly member_summaries(K * K)[i * K + j]'s number
+        (the same arithmetic: sums over max(completed, 1)). member_totals(K * K) on the device, then ONE host
+        copy for the whole matrix."""
+        from ..distributed import summarize_segments
+
+        K = int(nets)
+        if not 1 <= K <= MAX_MEMBERS:
+            raise ValueError(f"league_summary takes 1..{MAX_MEMBERS} nets, got {K}")
+        return {k: v.reshape(K, K) for k, v in summarize_segments(self.member_totals(K * K)).items()}
+
     def member_summaries(self, members: int):
         """episode_summary() of each of `members` equal slices of the batch (rollout_qnet_many's members): a
         list of the summaries the lone envs holding those slices would give."""

@@ -11,6 +11,7 @@ ring, seed, counters and hyperparameters:
     env = MergeVecEnv(8 * 1024, device="cuda:0")            # member m owns envs [1024 m, 1024 (m + 1))
     pop.collect(env, 16)                                    # every member acts with its own net and stores
     pop.learn(4)                                            # into its own ring; four updates of all eight
+    pay = pop.cross_play(league_env, 64)                    # [8, 8] payoff matrices: ego i against opponent j
     pop.copy_member(best, worst)                            # population-based training's exploit step
 
 Member m is bit for bit the lone DQNLearner built from the same net, ring, seed and hyperparameters:
@@ -126,6 +127,33 @@ class DQNPopulation(DQNNets):
                                      opp_episilo)
         store_rollout_many(self.rings, obs0, traj, skip_ego_won)
         return traj
+
+    # ------------------------------------------------------------------ evaluate
+    def cross_play(self, env, num_steps: int, seed=None, episilo=0.7):
+        """The league's payoff matrices: every member as ego against every member as opponent, K = len(self).
+        Exactly env.clear_statistics(), env.rollout_qnet_league(num_steps, self.qnets, seed, episilo,
+        trajectory=False) and env.league_summary(K): three launches (the rollout of all K^2 pairings, the two of
+        the segmented reduction) and one host copy, whatever K is. env holds K^2 slices of a multiple of 64
+        envs; pairing (i, j) plays on slice i K + j. seed: one value or K (None: the members' own seeds);
+        episilo: one value or K, each net's exploration on either side. Nothing is stored in the rings and the
+        learners are untouched; env's earlier statistics are cleared, and its envs move on num_steps steps.
+
+        Returns a dict with episode_summary()'s keys, each a [K, K] float64 CPU tensor (`completed`: int64):
+        entry [i, j] is that quantity over the episodes ego i completed against opponent j. Row i is how member
+        i fares as the ego, column i what the others achieve against it. A fitness for the exploit step:
+
+            pay = pop.cross_play(env, 64)
+            win, ret = pay["win_rate_main"], pay["mean_return_ego"]
+            fitness = win.mean(1) - win.mean(0) + 0.01 * (ret.mean(1) - ret.mean(0))   # [K]
+            pop.copy_member(int(fitness.argmax()), int(fitness.argmin()))
+
+        The diagonal is a member against a copy of itself (the other-net path, not opponent="self"). Frozen
+        checkpoints are evaluated by env.rollout_qnet_league(num_steps, self.qnets + frozen_qnets, ...) on an
+        env of (K + F)^2 slices and reading the sub-block of env.league_summary(K + F); there is no
+        rectangular form."""
+        env.clear_statistics()
+        env.rollout_qnet_league(num_steps, self.qnets, self.seed if seed is None else seed, episilo, trajectory=False)
+        return env.league_summary(len(self))
 
     # ------------------------------------------------------------------ learn
     def learn(self, num_updates: int = 1, filled_only: bool = False, return_loss: bool = False,
