@@ -71,6 +71,8 @@
  *                     half of a Rainbow population -- up to 64 members' rollouts on slices of one env batch
  *                     in one launch, and their transitions into 64 replay memories in two; every member bit
  *                     for bit a lone mg_rollout_rainbow / mg_rainbow_replay_store
+ *   mg_rollout_rainbow_vs / mg_rollout_rainbow_vs_many: that loop with action_op from a second Rainbow net
+ *                     (a frozen checkpoint, another member of the population), lone and per member
  *   mg_abi_version, mg_last_error, mg_build_info, mg_params_default, mg_time_next_launch: library plumbing
  *                     and profiling (no reference twin).
  *
@@ -848,8 +850,7 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
  * copying its member's net into LDS, the nets' addresses in the kernel argument, so a call allocates and
  * synchronises nothing. n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole,
  * so two members never share a wave or a word). opponent_mode 0 or 2 as mg_rollout_rainbow; cross-play (a
- * member against another member's net) is not offered: two Rainbow nets and the observation tile exceed one
- * CU's LDS. Refused before anything is read or launched, in this order: members outside 1 .. 64, n_member < 0,
+ * member against another member's net) is mg_rollout_rainbow_vs_many, below. Refused before anything is read or launched, in this order: members outside 1 .. 64, n_member < 0,
  * n_member % 64 != 0, members * n_member past the grid limit, what mg_rollout_rainbow refuses of params, state
  * and traj, nets NULL, a NULL or misaligned member net (the text names the member), num_steps outside
  * 0 .. 65535, opponent_mode other than 0 or 2, a misaligned traj buffer; then n_member == 0 or num_steps == 0
@@ -857,6 +858,40 @@ int mg_host_rainbow_exp(const float* x, float* y, int64_t n);
 int mg_rollout_rainbow_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
                             const mg_stats* stats, int64_t n_member, int32_t members, int32_t num_steps,
                             const void* const* nets, int32_t opponent_mode, uint32_t flags, void* stream);
+
+/* ---- Rainbow against another Rainbow net (additive to ABI 21) -----------------------------------------
+ * mg_rollout_rainbow_vs replaces :662-680 with action_op taken from a SECOND model -- action =
+ * current_model.act(state), action_op = other_model.act(state[3:] + state[:3]), env.step(action, action_op) --
+ * for num_steps steps in one launch: mg_rollout_rainbow's arguments with the opponent's packed net (`opponent`, as
+ * `net` a device pointer, 16-byte aligned, mg_rainbow_packed_bytes() long) in the place of opponent_mode. The
+ * contract is the composition's, bit for bit: at every step traj.a1 is mg_rainbow_forward(net, obs, rotate 0)'s
+ * action, traj.a2 is mg_rainbow_forward(opponent, obs, rotate 3)'s, and everything else is mg_step on those two
+ * actions (MFMA columns are independent and the head runs on registers, so a forward inside the rollout is the
+ * stand-alone forward's bits). opponent == net is allowed and is then bit for bit opponent_mode 2 of
+ * mg_rollout_rainbow: the diagonal of a pairing grid needs no other call.
+ * LDS of a 512-env block: the ego's whole net (74,192 B), the opponent's net from its value stream's bias on
+ * (both hidden streams, the six head streams, the support: 67,792 B) and the observation tile (20,480 B), 162,464
+ * of the CU's 163,840 B; the opponent's first two layers (6,400 B) are read from `opponent` in device memory at
+ * every forward, so `opponent` must stay unchanged while the launch runs, as `net` must.
+ * Refused before anything is read or launched, in this order: what mg_rollout_rainbow refuses of params, state,
+ * traj and n (the same texts), a NULL or misaligned net, a NULL or misaligned opponent, num_steps outside
+ * 0 .. 65535 (these three texts start with the call's name), a misaligned traj buffer; then n == 0 or num_steps
+ * == 0 returns 0 and launches nothing.
+ *
+ * mg_rollout_rainbow_vs_many is mg_rollout_rainbow_many with an opponent per member: member m acts with nets[m]
+ * against opponents[m] on its slice, bit for bit mg_rollout_rainbow_vs(nets[m], opponents[m]) on the slice
+ * alone. opponents is a host array of `members` device pointers like nets; entries may repeat, may be entries
+ * of nets, and opponents[m] == nets[m] is member m in self-play. A block of member m copies nets[m] and the stream
+ * part of opponents[m] into LDS; all the addresses travel in the kernel argument. Refused in
+ * mg_rollout_rainbow_many's order with this call's name in front: the member count and n_member checks, params /
+ * state / traj, nets NULL, a NULL or misaligned nets[m], opponents NULL, a NULL or misaligned opponents[m] (the
+ * text names the first such member), num_steps, a misaligned traj buffer. */
+int mg_rollout_rainbow_vs(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                          int64_t n, int32_t num_steps, const void* net, const void* opponent, uint32_t flags,
+                          void* stream);
+int mg_rollout_rainbow_vs_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                               const mg_stats* stats, int64_t n_member, int32_t members, int32_t num_steps,
+                               const void* const* nets, const void* const* opponents, uint32_t flags, void* stream);
 
 /* ---- Rainbow learning (additive to ABI 21) ----------------------------------------------------------
  * compute_td_loss (scripts/ranbowdqn.py:584-609) with projection_distribution (:554-582) on the device, and

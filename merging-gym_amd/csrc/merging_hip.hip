@@ -660,31 +660,54 @@ int mg_rollout_rainbow(const mg_params* params, const mg_state* state, const mg_
 int mg_rollout_rainbow_many(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
                             int64_t n_member, int32_t members, int32_t num_steps, const void* const* nets,
                             int32_t opponent_mode, uint32_t flags, void* stream) {
-  const char* const who = "mg_rollout_rainbow_many: %s";
-  if (!members_ok(members)) return fail(hipErrorInvalidValue, who, "need 1 <= members <= 64");
-  if (n_member < 0) return fail(hipErrorInvalidValue, who, "n_member < 0");
-  if (n_member % 64 != 0)
-    return fail(hipErrorInvalidValue, who,
-                "n_member must be a multiple of 64 (a won-mask word covers 64 envs and is stored whole, so no "
-                "two members may share one)");
-  if (n_member > (static_cast<int64_t>(0x7fffffff) * kBlock) / members)
-    return fail(hipErrorInvalidValue, who, "members * n_member exceeds the grid limit");
+  const char* const who = "mg_rollout_rainbow_many";
+  if (int e = check_rb_rollout_members(who, n_member, members)) return e;
   const int64_t n = n_member * members;
   if (int e = check_rollout_args(params, state, traj, n)) return e;
-  if (!nets) return fail(hipErrorInvalidValue, who, "nets is NULL (members packed Rainbow nets)");
-  for (int m = 0; m < members; ++m)
-    if (!nets[m] || misaligned(nets[m], 15))
-      return fail_member("mg_rollout_rainbow_many", m, "net must be a 16-byte aligned packed Rainbow net");
+  if (int e = check_rb_member_nets(who, nets, members, "net")) return e;
   if (int e = check_rb_rollout_steps_mode(true, num_steps, opponent_mode)) return e;
   if (int e = check_traj(traj)) return e;
   if (n_member == 0 || num_steps == 0) return 0;
-  RbRolloutMany A{make_rb_rollout(params, state, traj, stats, n, num_steps, flags), n_member,
-                  static_cast<int32_t>(grid_blocks(n_member, kRbThreads)), members};
-  for (int m = 0; m < members; ++m) A.net[m] = static_cast<const uint8_t*>(nets[m]);
-  launch(rainbow_rollout_instance<true>(opponent_mode),
-         static_cast<unsigned>(members) * static_cast<unsigned>(A.blocks_per_member), kRbThreads,
-         static_cast<hipStream_t>(stream), A);
-  return finish_launch("mg_rollout_rainbow_many");
+  return launch_rb_rollout_many(who, rainbow_rollout_instance<true>(opponent_mode),
+                                make_rb_rollout(params, state, traj, stats, n, num_steps, flags), n_member, members,
+                                nets, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int mg_rollout_rainbow_vs(const mg_params* params, const mg_state* state, const mg_traj* traj, const mg_stats* stats,
+                          int64_t n, int32_t num_steps, const void* net, const void* opponent, uint32_t flags,
+                          void* stream) {
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (int e = check_packed_net(net, "mg_rollout_rainbow_vs: net must be a 16-byte aligned packed Rainbow net"))
+    return e;
+  if (int e = check_packed_net(opponent,
+                               "mg_rollout_rainbow_vs: opponent must be a 16-byte aligned packed Rainbow net"))
+    return e;
+  if (int e = check_rb_rollout_steps("mg_rollout_rainbow_vs", num_steps)) return e;
+  if (int e = check_traj(traj)) return e;
+  if (n == 0 || num_steps == 0) return 0;
+  RbRolloutVs A{make_rb_rollout(params, state, traj, stats, n, num_steps, flags),
+                static_cast<const uint8_t*>(opponent)};
+  A.R.net = static_cast<const uint8_t*>(net);
+  launch(rainbow_rollout_kernel<3, false>, grid_blocks(n, kRbThreads), kRbThreads, static_cast<hipStream_t>(stream),
+         A);
+  return finish_launch("mg_rollout_rainbow_vs");
+}
+
+int mg_rollout_rainbow_vs_many(const mg_params* params, const mg_state* state, const mg_traj* traj,
+                               const mg_stats* stats, int64_t n_member, int32_t members, int32_t num_steps,
+                               const void* const* nets, const void* const* opponents, uint32_t flags, void* stream) {
+  const char* const who = "mg_rollout_rainbow_vs_many";
+  if (int e = check_rb_rollout_members(who, n_member, members)) return e;
+  const int64_t n = n_member * members;
+  if (int e = check_rollout_args(params, state, traj, n)) return e;
+  if (int e = check_rb_member_nets(who, nets, members, "net")) return e;
+  if (int e = check_rb_member_nets(who, opponents, members, "opponent")) return e;
+  if (int e = check_rb_rollout_steps(who, num_steps)) return e;
+  if (int e = check_traj(traj)) return e;
+  if (n_member == 0 || num_steps == 0) return 0;
+  return launch_rb_rollout_many(who, rainbow_rollout_kernel<3, true>,
+                                make_rb_rollout(params, state, traj, stats, n, num_steps, flags), n_member, members,
+                                nets, opponents, static_cast<hipStream_t>(stream));
 }
 
 int mg_host_rainbow_head(const float* logits, const float* support, float* q, int8_t* action, int64_t n) {

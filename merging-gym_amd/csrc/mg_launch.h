@@ -19,6 +19,13 @@ int fail(int code, const char* fmt, const char* what) {
   return code ? code : static_cast<int>(hipErrorInvalidValue);
 }
 
+// a refusal with the call's name in front; who == NULL gives the bare text
+int fail_in(const char* who, const char* text) {
+  if (who) std::snprintf(g_err, sizeof(g_err), "%s: %s", who, text);
+  else std::snprintf(g_err, sizeof(g_err), "%s", text);
+  return static_cast<int>(hipErrorInvalidValue);
+}
+
 // p is not aligned to mask + 1 bytes (a NULL pointer is aligned)
 bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 

@@ -239,17 +239,24 @@ __device__ __forceinline__ void rb_stream(const uint8_t* net, int boff, int woff
   }
 }
 
-// The forward of this wave's 64 envs from their fp32 observation rows wtile [64][10] in LDS, with the packed
-// net in LDS. rot: the view, input j = obs[(j + rot) % 10] (0 the ego's; 3 the opponent's state[3:] + state[:3]
-// of ranbowdqn.py:669). On return lane l holds q[0..4] and the chosen action of env l. logits (global,
-// [nrows][306] of this wave's envs, or NULL): the raw head outputs. Every lane of the wave must call it.
-__device__ __forceinline__ void rainbow_forward_wave(const uint8_t* net_lds, const float* wtile, int rot,
-                                                     float (&q)[kRbActions], int& action, float* logits, int nrows) {
+// The forward of this wave's 64 envs from their fp32 observation rows wtile [64][10] in LDS. The packed net is
+// named by two bases, each that of a whole packed net: `trunk` serves bytes [0, kRbOffBV1) (W1, b2, W2) and
+// `streams` bytes [kRbOffBV1, kRbNetBytes) (the hidden streams, the head, the support). With the whole net in LDS
+// both are that copy; a rollout against another net (rainbow_rollout_kernel<3>) keeps only the opponent's stream
+// part in LDS and reads its 6,400-byte trunk from the packed net in global memory. rot: the view, input j =
+// obs[(j + rot) % 10] (0 the ego's; 3 the opponent's state[3:] + state[:3] of ranbowdqn.py:669). On return lane l
+// holds q[0..4] and the chosen action of env l. logits (global, [nrows][306] of this wave's envs, or NULL): the
+// raw head outputs. Every lane of the wave must call it.
+__device__ __forceinline__ void rainbow_forward_wave(const uint8_t* trunk_base, const uint8_t* streams_base,
+                                                     const float* wtile, int rot, float (&q)[kRbActions], int& action,
+                                                     float* logits, int nrows) {
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   action = 0;
 #pragma unroll 1
   for (int t = 0; t < 4; ++t) {
-    const uint8_t* net = net_lds + opaque_zero();  // the fragment loads stay inside the loop
+    const int oz = opaque_zero();  // the fragment loads stay inside the loop
+    const uint8_t* trunk = trunk_base + oz;
+    const uint8_t* net = streams_base + oz;
     // layer-1 B operand: k = 8 g + j of env 16 t + c
     const float* row = wtile + (16 * t + c) * kObs;
     float xin[8];
@@ -268,13 +275,13 @@ __device__ __forceinline__ void rainbow_forward_wave(const uint8_t* net_lds, con
     const bf16x8 xb = __builtin_bit_cast(bf16x8, xw);
     const f32x4 z4 = {};
     // layer 1: 32 units, bias inside the K sum
-    const f32x4 a10 = mfma16(rb_frag(net, kRbOffW1), xb, z4);
-    const f32x4 a11 = mfma16(rb_frag(net, kRbOffW1 + kRbFrag), xb, z4);
+    const f32x4 a10 = mfma16(rb_frag(trunk, kRbOffW1), xb, z4);
+    const f32x4 a11 = mfma16(rb_frag(trunk, kRbOffW1 + kRbFrag), xb, z4);
     const bf16x8 h1 = rb_hidden(a10, a11);
     // layer 2: 64 units over one k-block
     f32x4 a2[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) a2[m] = mfma16(rb_frag(net, kRbOffW2 + kRbFrag * m), h1, rb_bias(net, kRbOffB2, m));
+    for (int m = 0; m < 4; ++m) a2[m] = mfma16(rb_frag(trunk, kRbOffW2 + kRbFrag * m), h1, rb_bias(trunk, kRbOffB2, m));
     const bf16x8 h2[2] = {rb_hidden(a2[0], a2[1]), rb_hidden(a2[2], a2[3])};
     // the two hidden streams
     f32x4 av[4], aa[4];
@@ -337,11 +344,12 @@ __device__ __forceinline__ void rainbow_forward_wave(const uint8_t* net_lds, con
   }
 }
 
-// Cooperative copy of a packed net into LDS (all threads of the block; caller syncs).
-__device__ __forceinline__ void rainbow_to_lds(const uint8_t* net, uint8_t* lds) {
+// Cooperative copy of a packed net, or of its first `bytes` (a multiple of 16) from `net` on, into LDS (all threads
+// of the block; caller syncs).
+__device__ __forceinline__ void rainbow_to_lds(const uint8_t* net, uint8_t* lds, int bytes = kRbNetBytes) {
   const f32x4* src = reinterpret_cast<const f32x4*>(net);
   f32x4* dst = reinterpret_cast<f32x4*>(lds);
-  for (int j = threadIdx.x; j < kRbNetBytes / 16; j += blockDim.x) dst[j] = src[j];
+  for (int j = threadIdx.x; j < bytes / 16; j += blockDim.x) dst[j] = src[j];
 }
 
 // Stand-alone forward (RainbowNet.forward / .act, and the test seam): obs [n][10] -> optional logits [n][306],
@@ -363,7 +371,7 @@ __global__ __launch_bounds__(kBlock) void rainbow_forward_kernel(const uint8_t* 
   const int wrows = wrem <= 0 ? 0 : (wrem < 64 ? static_cast<int>(wrem) : 64);
   float q[kRbActions];
   int act;
-  rainbow_forward_wave(lds_net, tile + (threadIdx.x & ~63) * kObs, rot, q, act,
+  rainbow_forward_wave(lds_net, lds_net, tile + (threadIdx.x & ~63) * kObs, rot, q, act,
                        logits ? logits + wbase * kRbLogits : nullptr, wrows);
   const int64_t i = base + threadIdx.x;
   if (i < n) {

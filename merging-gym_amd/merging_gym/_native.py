@@ -310,6 +310,13 @@ def _load(path=LIB_PATH):
     lib.mg_host_rainbow_replay_store_many.argtypes = rl_store_many
     for f in (lib.mg_rollout_rainbow_many, lib.mg_rainbow_replay_store_many, lib.mg_host_rainbow_replay_store_many):
         f.restype = _c.c_int
+    # Rainbow against another Rainbow net (additive to ABI 21): the opponent's packed net in opponent_mode's place
+    lib.mg_rollout_rainbow_vs.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _P, _P,
+                                          _c.c_uint32, _P]
+    lib.mg_rollout_rainbow_vs_many.argtypes = [PP, SP, _c.POINTER(Traj), STP, _c.c_int64, _c.c_int32, _c.c_int32,
+                                               _c.POINTER(_P), _c.POINTER(_P), _c.c_uint32, _P]
+    for f in (lib.mg_rollout_rainbow_vs, lib.mg_rollout_rainbow_vs_many):
+        f.restype = _c.c_int
     # a population of prioritized Rainbow learners (additive to ABI 21): learn with every member's tree, the store
     PM = _c.POINTER(PerMember)
     per_many = [PM, _c.c_size_t, _P, _P]

@@ -508,16 +508,35 @@ class MergeVecEnv:
         n = self.num_envs // M
         return [summarize(self.returns[m * n:(m + 1) * n], self.counts[m * n:(m + 1) * n]) for m in range(M)]
 
-    def rollout_rainbow(self, num_steps: int, net, opponent: str = "self", final_observation: bool = True,
+    def _rainbow_opponent_packed(self, opp):
+        """The packed bytes of a RainbowNet given as a rollout's opponent, on this env's device."""
+        packed = opp.packed
+        if packed.device != self.device:
+            raise ValueError(f"the opponent net lives on {packed.device}, the env on {self.device}")
+        return packed
+
+    def rollout_rainbow(self, num_steps: int, net, opponent="self", final_observation: bool = True,
                         won_mask: bool = True):
         """`num_steps` steps of ranbowdqn.py's acting loop (:662-680) in one launch: action =
         current_model.act(state) (:668) on the device (`net`, a RainbowNet: bf16 MFMA layers, the
         distributional head in fp32), fused with the env step. opponent: "self" (:669, the same net on the
-        view state[3:] + state[:3]) or "none" (action_op = None, the env's own L0 opponent). There is no
-        draw: the exploration is in the net's noise buffers (RainbowNet.reset_noise). Returns the same
+        view state[3:] + state[:3]), "none" (action_op = None, the env's own L0 opponent), or another RainbowNet
+        on this device (action_op = that net's act on state[3:] + state[:3]: a frozen checkpoint, another
+        learner's net; `net` itself gives "self" to the bit); any other string is a KeyError. There is no
+        draw: the exploration is in the nets' noise buffers (RainbowNet.reset_noise). Returns the same
         [T, N, ...] dict as rollout_qnet; the episode statistics' r1 sums are the script's episode_reward."""
+        from ..rainbow import RainbowNet
+
         nat = self._nat
         T, n = int(num_steps), self.num_envs
+        if isinstance(opponent, RainbowNet):
+            other = self._rainbow_opponent_packed(opponent)
+            buf = self._traj(T, final_observation, won_mask)
+            rc = nat.lib.mg_rollout_rainbow_vs(self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, n,
+                                               T, net.packed.data_ptr(), other.data_ptr(), self._flags,
+                                               self._stream())
+            nat.check(rc, "mg_rollout_rainbow_vs")
+            return buf["_result"]
         mode = {"none": 0, "self": 2}[opponent]
         buf = self._traj(T, final_observation, won_mask)
         rc = nat.lib.mg_rollout_rainbow(self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]), self._st_ref, n, T,
@@ -525,14 +544,15 @@ class MergeVecEnv:
         nat.check(rc, "mg_rollout_rainbow")
         return buf["_result"]
 
-    def rollout_rainbow_many(self, num_steps: int, nets, opponent: str = "self", final_observation: bool = True,
+    def rollout_rainbow_many(self, num_steps: int, nets, opponent="self", final_observation: bool = True,
                              won_mask: bool = True):
         """rollout_rainbow for M actors in ONE launch: nets is a list of M RainbowNets, and member m owns envs
         [m n, (m + 1) n), n = num_envs / M (a multiple of 64: a won-mask word never spans two members), where it
-        acts with nets[m]. opponent: "self" or "none" for every member (cross-play is not offered: two Rainbow
-        nets and the observation tile exceed one CU's LDS). There is no draw, so member m's slice is bit for bit
-        what a lone MergeVecEnv(n) holding the slice's state gives for rollout_rainbow(num_steps, nets[m],
-        opponent). Returns the same [T, N, ...] dict as rollout_rainbow (rainbow_learn.store_rainbow_rollout_many
+        acts with nets[m]. opponent: "self" or "none" for every member, or a list of M RainbowNets, member m
+        playing against opponent[m] (entries may repeat and may be members of `nets`: cross-play, or a frozen
+        checkpoint for all). There is no draw, so member m's slice is bit for bit what a lone MergeVecEnv(n)
+        holding the slice's state gives for rollout_rainbow(num_steps, nets[m], opponent) -- opponent[m] where it
+        is a list. Returns the same [T, N, ...] dict as rollout_rainbow (rainbow_learn.store_rainbow_rollout_many
         appends it to M replays in place). The nets' addresses travel in the kernel argument: a call allocates
         and synchronises nothing."""
         nat = self._nat
@@ -544,6 +564,18 @@ class MergeVecEnv:
             raise ValueError(f"num_envs = {self.num_envs} must be {M} slices of a multiple of 64 envs (a won-mask "
                              "word covers 64 envs, so two members must not share one)")
         T = int(num_steps)
+        if not isinstance(opponent, str):
+            others = [self._rainbow_opponent_packed(o) for o in opponent]
+            if len(others) != M:
+                raise ValueError(f"{M} nets need {M} opponents (one per member), got {len(others)}")
+            buf = self._traj(T, final_observation, won_mask)
+            packed = (ctypes.c_void_p * M)(*(net.packed.data_ptr() for net in nets))
+            against = (ctypes.c_void_p * M)(*(o.data_ptr() for o in others))
+            rc = nat.lib.mg_rollout_rainbow_vs_many(self._p_ref, self._s_ref, ctypes.byref(buf["_traj"]),
+                                                    self._st_ref, self.num_envs // M, M, T, packed, against,
+                                                    self._flags, self._stream())
+            nat.check(rc, "mg_rollout_rainbow_vs_many")
+            return buf["_result"]
         mode = {"none": 0, "self": 2}[opponent]
         buf = self._traj(T, final_observation, won_mask)
         packed = (ctypes.c_void_p * M)(*(net.packed.data_ptr() for net in nets))

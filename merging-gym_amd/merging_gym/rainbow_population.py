@@ -31,9 +31,13 @@ lone PrioritizedRainbowLearner(..., generator=DeviceNoise(noise_seed[m])):
     pop.collect(env, 16)
     pop.learn(4, beta=0.5)                                  # beta per call: one value, or one per member
 
-Not part of these classes: cross-play (a member against another member's net: two Rainbow nets and the observation
-tile exceed one CU's LDS), appending to the replays from inside the rollout kernel, and a target sync by episode
-count (the caller reads env.member_summaries and calls sync_target).
+Members may meet each other or a frozen checkpoint: collect(env, T, opponent=[1, 0, checkpoint, ...]) gives member
+m the current acting net of the member named by an index, or the RainbowNet given, as its opponent
+(mg_rollout_rainbow_vs_many); the stored rows stay the ego's.
+
+Not part of these classes: a league (a K x K grid of pairings in one launch), an epsilon mixture on top of the
+noisy nets, storing the opponent's view of the transitions, appending to the replays from inside the rollout
+kernel, and a target sync by episode count (the caller reads env.member_summaries and calls sync_target).
 """
 
 from __future__ import annotations
@@ -182,15 +186,29 @@ class RainbowPopulation:
         return [int(s) for s in self._noise_seeds]
 
     # ------------------------------------------------------------------ act and store
-    def collect(self, env, num_steps: int, opponent: str = "self"):
+    def collect(self, env, num_steps: int, opponent="self"):
         """The acting half of the loop for every member at once: env.observe(), one
         env.rollout_rainbow_many(num_steps, self.nets, opponent) -- member m on its slice of env's batch -- and one
         store_rainbow_rollout_many into self.replays: four launches beside the 4 M of the members in turn, each
-        member's slice, replay and counter bit for bit the lone loop's. Returns the trajectory. Refuses a
-        population whose replays are shared."""
+        member's slice, replay and counter bit for bit the lone loop's. opponent: "self" or "none" for every
+        member, or a list of M items, item m a member index (member m plays against that member's current acting
+        net: cross-play) or a RainbowNet (a frozen checkpoint); an index outside 0 .. M - 1 is a ValueError. The
+        stored rows are the ego's either way. Returns the trajectory. Refuses a population whose replays are
+        shared."""
         if len({id(r) for r in self.replays}) != len(self.replays):
             raise ValueError("collect() appends each member's transitions to its own ring: this population's "
                              "rings are shared")
+        if not isinstance(opponent, str):
+            M = len(self.nets)
+            opponent = list(opponent)
+            if len(opponent) != M:
+                raise ValueError(f"{M} members need {M} opponents (one per member), got {len(opponent)}")
+            for m, o in enumerate(opponent):
+                if isinstance(o, RainbowNet):
+                    continue
+                if isinstance(o, bool) or not isinstance(o, int) or not 0 <= o < M:
+                    raise ValueError(f"opponent[{m}] = {o!r}: a member index in 0..{M - 1} or a RainbowNet")
+                opponent[m] = self.nets[o]
         obs0 = env.observe()
         traj = env.rollout_rainbow_many(num_steps, self.nets, opponent)
         self._store_many(self.replays, obs0, traj)

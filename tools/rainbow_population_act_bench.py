@@ -1,7 +1,7 @@
 """Time of the acting half of a Rainbow population's loop on the device (not part of bench.py).
 
     python tools/rainbow_population_act_bench.py [--out profiles/rainbow_population_act_bench.json]
-                                                 [--window 0.3] [--repeats 3]
+                                                 [--window 0.3] [--repeats 3] [--vs]
 
 The method is tools/population_act_bench.py's. One iteration is observe + a rollout at T = 16 + the store into
 replays of 10,000 rows, for M members of n_member envs:
@@ -17,6 +17,10 @@ are kept, and spread = (max - min) / min of a side's own repeats. not_slower: ma
 of the two spreads).
   member_indexing   M = 1 at N = 2^20 beside the lone kernel on the same env (rollout only, and rollout + store):
                     what the member indexing itself costs.
+  --vs              the "vs another net" leg alone, merged into the --out file as "vs_points" (every other key
+                    stays): member m against the net of member (m + 1) % M -- rollout_rainbow_many(T, nets,
+                    opponent=[...]) beside M lone rollout_rainbow(T, nets[m], opponent=nets[(m + 1) % M]) + store in
+                    turn -- for M in {2, 8, 64} at 1,024 envs per member.
 The nets are the reference's initialisation with drawn noise and the envs start from reset: with autoreset the mix
 of states settles within the warm-up, and both sides see the same states (the member launch equals the lone ones
 bit for bit).
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rainbow_population_act_bench.json"))
     ap.add_argument("--window", type=float, default=0.3)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--vs", action="store_true", help="only the cross-play leg, merged into --out as vs_points")
     args = ap.parse_args()
 
     import torch
@@ -63,25 +68,35 @@ def main():
         all_nets.append(RainbowNet.from_state_dict({k: v.detach() for k, v in current.state_dict().items()},
                                                    device=dev))
         all_nets[-1].packed  # packed now, outside every window
-    result = {"device": torch.cuda.get_device_name(0), "build": _native.build_info(), "T": T, "capacity": CAP,
-              "window_s": args.window, "repeats": args.repeats, "points": []}
+    setup = {"device": torch.cuda.get_device_name(0), "build": _native.build_info(), "T": T, "capacity": CAP,
+             "window_s": args.window, "repeats": args.repeats}
+    result = dict(setup, points=[])
+    points = result["points"]
+    if args.vs:
+        with open(args.out) as f:
+            result = json.load(f)
+        result["vs_setup"] = setup
+        points = result["vs_points"] = []
     for M in MEMBERS:
-        for n in N_MEMBER:
+        for n in N_MEMBER[:1] if args.vs else N_MEMBER:
             env = MergeVecEnv(M * n, device=dev)
             envs = [MergeVecEnv(n, device=dev) for _ in range(M)]
             replays = [RainbowReplay(CAP, device=dev) for _ in range(M)]
             lone_replays = [RainbowReplay(CAP, device=dev) for _ in range(M)]
             nets = all_nets[:M]
-            for opponent in ("none", "self"):
+            against = [nets[(m + 1) % M] for m in range(M)]
+            for opponent in ("next_member",) if args.vs else ("none", "self"):
 
                 def many():
                     obs0 = env.observe()
-                    store_rainbow_rollout_many(replays, obs0, env.rollout_rainbow_many(T, nets, opponent))
+                    opp = against if args.vs else opponent
+                    store_rainbow_rollout_many(replays, obs0, env.rollout_rainbow_many(T, nets, opp))
 
                 def lone():
                     for m in range(M):
                         obs0 = envs[m].observe()
-                        lone_replays[m].store_rollout(obs0, envs[m].rollout_rainbow(T, nets[m], opponent))
+                        opp = against[m] if args.vs else opponent
+                        lone_replays[m].store_rollout(obs0, envs[m].rollout_rainbow(T, nets[m], opp))
 
                 (many_us, lone_us), iters = windows(torch, (many, lone), args.window, args.repeats)
                 tol = max(spread(many_us), spread(lone_us))
@@ -91,10 +106,17 @@ def main():
                          "speedup": min(lone_us) / min(many_us),
                          "many_env_steps_per_s": M * n * T / (min(many_us) * 1e-6),
                          "not_slower": min(many_us) <= min(lone_us) * (1.0 + tol)}
-                result["points"].append(point)
+                points.append(point)
                 print(json.dumps(point), flush=True)
             del env, envs, replays, lone_replays
             torch.cuda.empty_cache()
+    if args.vs:
+        result["vs_not_slower_at_every_point"] = all(p["not_slower"] for p in points)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"merged vs_points into {args.out}")
+        return
     # what the member indexing itself costs: one member on 2^20 envs beside the lone kernel, the same env
     env = MergeVecEnv(1 << 20, device=dev)
     replay = RainbowReplay(CAP, device=dev)
